@@ -6,7 +6,15 @@ Workload (BASELINE.json configs[1], SURVEY.md 8d "C2"): examples/cornell-box.bli
 step.  A ray is one traversal query (camera + continuation closest-hit, BSDF-MIS closest-hit,
 light-sample shadow any-hit); value = rays traced by all ranks / max-over-ranks wall time.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--no-cpu]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--dump-outputs DIR] [--full [--no-cpu]]
+
+A plain run sets up, warms up, times the K steps and prints the result line; its roofline object is
+arithmetic on the timed steps' own kernel times and the committed profiles/ (no run of its own).
+`--full` adds what takes work of its own: the CPU baseline (the oracle on a sample of the same pass).
+`--dump-outputs DIR` writes what the timed path handed back after its last step: DIR/film.npy, the
+accumulated film (height x width x [weight, r, g, b], float32) of the warm-up and timed passes, and
+DIR/pass_stats.npy, the last step's counters (float64, in the order of DUMP_STATS).  A film above
+32 MiB (C4, C5) is written as a fixed, seeded sample of its pixels (dump_outputs).
 
 Multi-GPU: one process per GPU.  `--gpus N` without a torch.distributed
 environment re-launches this script under `torch.distributed.run` with N ranks before anything
@@ -56,6 +64,10 @@ SHADE_BYTES_SHADOW, SHADE_BYTES_MIS, SHADE_BYTES_SPECTRUM = 32 + 4, 8, 2 * 64
 FT_FACTORED = (1 << 0) | (1 << 6) | (1 << 12)
 SEED = 0x0B11A6
 DIGEST = None          # source_digest() of this tree, set by main()
+# the last step's counters written by --dump-outputs (summed over ranks), in this order
+DUMP_STATS = ("camera_samples", "rays_camera", "rays_continuation", "rays_mis", "rays_shadow", "path_vertices",
+              "dropped_samples")
+DUMP_MAX_BYTES = 32 << 20   # of film.npy; a larger film is sampled (--dump-outputs stays far below 64 MB)
 
 
 # ---------------------------------------------------------------- launcher
@@ -370,6 +382,23 @@ def shade_roofline(cfg, tot, steps, features):
     return out
 
 
+def dump_outputs(outdir: str, film_acc, height: int, width: int, last_stats, max_bytes: int = DUMP_MAX_BYTES) -> None:
+    """--dump-outputs: the film the timed path accumulated into (rank 0's, every rank's tiles merged)
+    and the last step's counters, as .npy files (16 MiB for the 1024 x 1024 film).  A film above
+    max_bytes (C4, C5) is written as a fixed, seeded sample of its pixels: film.npy is then n x 4 and
+    film_pixels.npy holds the pixels' row-major indices (float64, exact)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    film = film_acc.detach().cpu().numpy().astype(np.float32, copy=False).reshape(height, width, 4)
+    if film.nbytes > max_bytes:
+        n = max(1, max_bytes // 16)
+        idx = np.sort(np.random.default_rng(SEED).choice(height * width, size=n, replace=False))
+        film = film.reshape(-1, 4)[idx]
+        np.save(os.path.join(outdir, "film_pixels.npy"), idx.astype(np.float64))
+    np.save(os.path.join(outdir, "film.npy"), film)
+    np.save(os.path.join(outdir, "pass_stats.npy"), np.asarray(last_stats, dtype=np.float64))
+
+
 # ---------------------------------------------------------------- main
 def main():
     ap = argparse.ArgumentParser()
@@ -378,11 +407,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="C2")
     ap.add_argument("--chunk", type=int, default=0, help="paths in flight per wave (0 = library default)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the accumulated film and the last step's counters "
+                         "to DIR/film.npy and DIR/pass_stats.npy")
     ap.add_argument("--tile-stride", type=int, default=1,
                     help="render every k-th tile only (a bounded sample of huge configs such as C5; "
                          "reported in config.sample; never the default)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     global DIGEST
     DIGEST = source_digest()
 
@@ -466,10 +502,14 @@ def main():
         tot["ms_film"] += st.ms_film; tot["vertices"] += st.path_vertices; tot["dropped"] += st.dropped_samples
         tot["ms_closest"] += st.ms_closest; tot["n_closest"] += st.closest_launches
         tot["ms_shade"] += st.ms_shade; tot["n_shade"] += st.shade_launches
+    last = [float(getattr(sts[-1], k)) for k in DUMP_STATS]
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+        lv = torch.tensor(last, dtype=torch.float64, device=dev)
+        dist.all_reduce(lv, op=dist.ReduceOp.SUM)
+        last = lv.tolist()
         keys = sorted(tot)
         v = torch.tensor([float(tot[k]) for k in keys], dtype=torch.float64, device=dev)
         dist.all_reduce(v, op=dist.ReduceOp.SUM)
@@ -478,6 +518,8 @@ def main():
         dist.destroy_process_group()
         return
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, film_acc, job.height, job.width, last)
     mrays = tot["rays"] / elapsed / 1e6
     acc = film_acc.view(-1, 4)
     line = {
@@ -506,7 +548,7 @@ def main():
     if per_rank is not None:
         # worst / best rank render time, the gather (with its synchronize) and rank 0's merge per step
         line["config"]["per_rank"] = per_rank
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         line["cpu_baseline"] = cpu_baseline(args.config, CPU_STRIDE.get(args.config, 16))
     else:
         line["cpu_baseline"] = None

@@ -145,6 +145,41 @@ def test_gpus_flag_spawns_ranks(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_dump_outputs_writes_the_film_and_the_last_steps_counters(tmp_path):
+    """--dump-outputs: film.npy is the accumulated film as height x width x 4 binary32, pass_stats.npy
+    the last step's counters in DUMP_STATS order as binary64; an existing directory is reused."""
+    import bench
+    h, w = 3, 5
+    film = torch.arange(h * w * 4, dtype=torch.float32) * 0.25
+    last = [float(k + 1) for k in range(len(bench.DUMP_STATS))]
+    for _ in range(2):
+        bench.dump_outputs(str(tmp_path / "out"), film, h, w, last)
+    f = np.load(tmp_path / "out" / "film.npy")
+    s = np.load(tmp_path / "out" / "pass_stats.npy")
+    assert f.dtype == np.float32 and f.shape == (h, w, 4)
+    np.testing.assert_array_equal(f.reshape(-1), film.numpy())
+    assert s.dtype == np.float64 and s.tolist() == last
+    assert sorted(os.listdir(tmp_path / "out")) == ["film.npy", "pass_stats.npy"]
+    # a film above the size limit: the same seeded sample of pixels on every call, with their indices
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), film, h, w, last, max_bytes=6 * 16)
+    fa, ia = np.load(tmp_path / "a" / "film.npy"), np.load(tmp_path / "a" / "film_pixels.npy")
+    assert fa.dtype == np.float32 and fa.shape == (6, 4) and ia.dtype == np.float64
+    assert len(set(ia.tolist())) == 6 and ia.min() >= 0 and ia.max() < h * w and (np.diff(ia) > 0).all()
+    np.testing.assert_array_equal(fa, f.reshape(-1, 4)[ia.astype(np.int64)])
+    np.testing.assert_array_equal(ia, np.load(tmp_path / "b" / "film_pixels.npy"))
+    np.testing.assert_array_equal(fa, np.load(tmp_path / "b" / "film.npy"))
+
+
+def test_steps_must_be_positive(monkeypatch, capsys):
+    import bench
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit) as ex:
+        bench.main()
+    assert ex.value.code == 2 and "--steps" in capsys.readouterr().err
+
+
 def test_gpus_flag_must_match_world(monkeypatch):
     import bench
     monkeypatch.setenv("WORLD_SIZE", "2")

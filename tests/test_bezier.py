@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 from bling_amd.scene import ParseError, load_config, parse_job  # noqa: E402
 
 f32 = np.float32
-REF_EXAMPLES = "/root/reference/examples"
+REF_EXAMPLES = os.path.join(ROOT, "tests", "golden", "ref_scenes")   # the reference's scenes, as shipped
 HDR = os.path.join(ROOT, "fixtures", "scenes", "envmaps", "sky-synth.hdr")
 
 
@@ -117,7 +117,6 @@ def test_patch_needs_48_values():
             parse_job(p)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_EXAMPLES), reason="reference examples absent (GPU box)")
 @pytest.mark.parametrize("name,tris", [("gumbo", 51 * 2 * 16 * 16), ("environment", 0), ("crystal", 0)])
 def test_reference_scenes_load_with_the_fixture_map(name, tris):
     """environment.bling reads an .hdr from its author's home directory; gumbo.bling and crystal.bling

@@ -24,7 +24,7 @@ streams() {
 }
 measure() {
   local C=$1
-  timeout -k 10 300 python -u bench.py --config $C > $O/${C}_bench.log 2>&1
+  timeout -k 10 300 python -u bench.py --full --config $C > $O/${C}_bench.log 2>&1
   tail -1 $O/${C}_bench.log | cut -c1-160
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${C}_prof -o prof -- python3 bench.py --config $C --no-cpu > $O/${C}_prof.log 2>&1
   timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/${C}_pmc_fetch -o pmc -- python3 bench.py --config $C --no-cpu --steps 1 --warmup 0 > $O/${C}_pmc_fetch.log 2>&1
@@ -51,10 +51,10 @@ else
   streams C4
   measure C4
   C5A="--tile-stride 1024"
-  timeout -k 10 300 python -u bench.py --config C5 $C5A > $O/C5_bench.log 2>&1
+  timeout -k 10 300 python -u bench.py --full --config C5 $C5A > $O/C5_bench.log 2>&1
   tail -1 $O/C5_bench.log | cut -c1-160
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/C5_prof -o prof -- python3 bench.py --config C5 $C5A --no-cpu > $O/C5_prof.log 2>&1
-  timeout -k 10 300 python -u bench.py --config C1 > $O/C1_bench.log 2>&1
+  timeout -k 10 300 python -u bench.py --full --config C1 > $O/C1_bench.log 2>&1
   tail -1 $O/C1_bench.log | cut -c1-160
   sq C4
   sq C3

@@ -11,6 +11,6 @@ mkdir -p $O
 timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method thread tests -m gpu > $O/gpu_tests.log 2>&1
 cp gpurun_out/parity_metrics.jsonl $O/parity_metrics.jsonl
 tail -1 $O/gpu_tests.log
-timeout -k 10 300 python -u bench.py --config C1 > $O/C1_bench.log 2>&1
+timeout -k 10 300 python -u bench.py --full --config C1 > $O/C1_bench.log 2>&1
 tail -1 $O/C1_bench.log | cut -c1-120
 bash tools/r02_profile.sh $TAG

@@ -14,7 +14,7 @@ timeout -k 10 1000 python -u -m pytest tests -m gpu -v --timeout 240 --timeout-m
 rc=$?
 echo "tests rc=$rc"; tail -3 $O/${TAG}_gpu_tests.log
 if [ $rc -gt 1 ]; then exit $rc; fi
-timeout -k 10 300 python -u bench.py > $O/${TAG}_bench.log 2>&1 || exit $?
+timeout -k 10 300 python -u bench.py --full > $O/${TAG}_bench.log 2>&1 || exit $?
 tail -1 $O/${TAG}_bench.log
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof -o prof -- python3 bench.py --no-cpu > $O/${TAG}_prof_bench.log 2>&1 || exit $?
 echo done

@@ -13,10 +13,10 @@ SQA="SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VAL
 SQB="SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM SQ_WAVES"
 
 
-timeout -k 10 300 python -u bench.py --config C1 > $O/C1_bench.log 2>&1
+timeout -k 10 300 python -u bench.py --full --config C1 > $O/C1_bench.log 2>&1
 tail -1 $O/C1_bench.log | cut -c1-160
 for C in C2 C3 C4; do
-  timeout -k 10 300 python -u bench.py --config $C > $O/${C}_bench.log 2>&1
+  timeout -k 10 300 python -u bench.py --full --config $C > $O/${C}_bench.log 2>&1
   tail -1 $O/${C}_bench.log | cut -c1-160
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${C}_prof -o prof -- python3 bench.py --config $C --no-cpu > $O/${C}_prof.log 2>&1
   timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/${C}_pmc_fetch -o pmc -- python3 bench.py --config $C --no-cpu --steps 1 --warmup 0 > $O/${C}_pmc_fetch.log 2>&1
@@ -30,7 +30,7 @@ timeout -s KILL 200 rocprofv3 --pmc $SQA --output-format csv -d $O/C4_sqa -o pmc
 timeout -s KILL 200 rocprofv3 --pmc $SQB --output-format csv -d $O/C4_sqb -o pmc -- python3 bench.py --config C4 --no-cpu --steps 1 --warmup 0 > $O/C4_sqb.log 2>&1
 echo C4 sq ok
 C5A="--config C5 --tile-stride 1024"
-timeout -k 10 300 python -u bench.py $C5A > $O/C5_bench.log 2>&1
+timeout -k 10 300 python -u bench.py --full $C5A > $O/C5_bench.log 2>&1
 tail -1 $O/C5_bench.log | cut -c1-160
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/C5_prof -o prof -- python3 bench.py $C5A --no-cpu > $O/C5_prof.log 2>&1
 timeout -s KILL 250 rocprofv3 --pmc $SQA --output-format csv -d $O/C5_sqa -o pmc -- python3 bench.py $C5A --no-cpu --steps 1 --warmup 0 > $O/C5_sqa.log 2>&1
