@@ -70,7 +70,9 @@ void plan_lds4(DevScene& S, uint32_t nodes, uint32_t tris, uint32_t refs, uint32
   // shape records (176 B each) go to LDS whole when the scene has a few: cornell's light quad
   const uint32_t sh = shapes <= kLdsShapesMax ? shapes : 0u;
   S.lds4_shapes = sh;
-  if (lds_bytes4(nodes, tris, refs, need, sh, false) <= kBudget) {
+  // all in LDS: decided with the size the all-LDS kernels launch with (their leaf-order layout and
+  // its two spare stack rows), so an lds_all4 block never exceeds the budget
+  if (lds_bytes4_leaf(nodes, refs, need, sh) <= kBudget) {
     S.lds4_nodes = nodes; S.lds4_tris = tris; S.lds4_refs = refs; S.stack4_lds = need;
     return;
   }
@@ -1126,9 +1128,11 @@ int bling_debug_scene_info(bling_ctx* c, char* buf, size_t size, size_t* len) {
   const int n = std::snprintf(tmp, sizeof tmp,
       "{\"prims\": %u, \"bvh_depth\": %d, \"bvh_leaves\": %d, \"bvh4_nodes\": %u, \"bvh4_depth\": %d, "
       "\"stack4_need\": %u, \"lds_all4\": %d, \"lds_trace4\": %zu, \"pkt_n\": %u, \"bf_prims\": %u, \"sh_inline\": %u, "
-      "\"lds_shade\": %zu, \"features\": %u}",
+      "\"lds_shade\": %zu, \"features\": %u, \"stack4_lds\": %u, \"lds4_shapes\": %u, \"lds4_tris\": %u, "
+      "\"lds4_nodes\": %u, \"max_leaf\": %d, \"sample_major\": %u}",
       c->num_prims, c->bvh_depth, c->bvh_leaves, S.num_nodes4, c->bvh4_depth, S.stack4_need, c->lds_all4 ? 1 : 0,
-      c->lds_trace4, S.pkt_n, S.bf_tris + S.bf_shapes, S.sh_inline, c->lds_shade, c->features);
+      c->lds_trace4, S.pkt_n, S.bf_tris + S.bf_shapes, S.sh_inline, c->lds_shade, c->features, S.stack4_lds,
+      S.lds4_shapes, S.lds4_tris, S.lds4_nodes, c->bvh_max_leaf, S.sample_major);
   if (n < 0) { g_err = "format error"; return BLING_EINVAL; }
   if (len) *len = (size_t)n;
   if (buf && size) { std::strncpy(buf, tmp, size - 1); buf[size - 1] = '\0'; }
