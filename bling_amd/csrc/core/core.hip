@@ -33,8 +33,6 @@ constexpr uint32_t kBruteMax = 16;
 static_assert(2 * kPacketMaxEntries <= 64, "the packet kernels hold the entry list in one VGPR float4 per lane");
 // scenes with at most this many analytic shapes keep their shape records in the BVH4 kernels' LDS
 constexpr uint32_t kLdsShapesMax = 8;
-// dynamic LDS of the shading kernel's in-line shadow test: 4 blocks x (36 KiB ring + 4 KiB) = 160 KiB
-constexpr size_t kShadeLdsMax = 4096;
 
 // LDS plan of the traversal kernels: keep a block at <= 30 KiB so five 256-thread blocks fit a CU's
 // 160 KiB.  The stack takes depth x 1 KiB; small scenes then go to LDS whole, larger ones keep the
@@ -62,8 +60,8 @@ void plan_lds(DevScene& S, uint32_t nodes, uint32_t tris, uint32_t refs, uint32_
 // triangles, refs and the whole stack bound fit, everything goes to LDS (lds_all4).  Otherwise
 // stack4_lds rows of the stack stay in LDS (12: flat from 8 to 20 rows on C3), the
 // rest spill to global rows, and the breadth-first node prefix (and the refs, if small) take what is
-// left (node_b bytes a node: 112, or 64 quantized in BLING_QBVH4 experiment builds).
-void plan_lds4(DevScene& S, uint32_t nodes, uint32_t tris, uint32_t refs, uint32_t need, uint32_t shapes, size_t node_b) {
+// left (112 bytes a node).
+void plan_lds4(DevScene& S, uint32_t nodes, uint32_t tris, uint32_t refs, uint32_t need, uint32_t shapes) {
   constexpr size_t kBudget = (size_t)26 * 1024;
   const size_t ref_b = (size_t)16 * ((refs + 3) / 4);
   S.stack4_need = need;
@@ -83,7 +81,7 @@ void plan_lds4(DevScene& S, uint32_t nodes, uint32_t tris, uint32_t refs, uint32
   S.lds4_tris = 0;
   S.lds4_refs = ref_b <= avail / 4 ? refs : 0;
   const size_t left = avail - (S.lds4_refs ? ref_b : 0);
-  S.lds4_nodes = (uint32_t)std::min<size_t>(nodes, left / node_b);
+  S.lds4_nodes = (uint32_t)std::min<size_t>(nodes, left / 112);
 }
 
 // Everything upload_scene and the kernels assume of a scene description, checked on the host before
@@ -280,9 +278,10 @@ void upload_scene(bling_ctx* c, const bling_scene_desc* d) {
   c->nodes.upload(reinterpret_cast<const float4*>(R.nodes.data()), R.nodes.size() / 4);
   c->refs.upload(R.refs.data(), R.refs.size());
   {
-    // the primitives' records in leaf order, the ref in each (dev_trace.h LeafRec): the BVH4 kernels
-    // with a global fallback test a leaf primitive with one dependent load instead of two
-    std::vector<float4> lg((size_t)3 * (R.refs.size() + 1), make_float4(0.f, 0.f, 0.f, 0.f));
+    // the primitives' records in leaf order, the ref in each, one zero record behind them (the layout:
+    // dev_trace.h LeafRec).  The BVH4 kernels with a global fallback test a leaf primitive with one
+    // dependent load instead of two; the all-LDS kernels copy the records into LDS as they are.
+    std::vector<float4> lg(leaf_geo_quads((uint32_t)R.refs.size()), make_float4(0.f, 0.f, 0.f, 0.f));
     for (size_t j = 0; j < R.refs.size(); ++j) {
       const uint32_t ref = R.refs[j], idx = ref & 0x3FFFFFFFu;
       if ((ref >> 30) == REF_TRI) { lg[3 * j] = geo[3 * idx]; lg[3 * j + 1] = geo[3 * idx + 1]; }
@@ -291,6 +290,7 @@ void upload_scene(bling_ctx* c, const bling_scene_desc* d) {
       lg[3 * j + 2] = make_float4((ref >> 30) == REF_TRI ? geo[3 * idx + 2].x : 0.f, rf, 0.f, 0.f);
     }
     c->leaf_geo.upload(lg.data(), lg.size());
+    if (c->leaf_geo.n != (size_t)3 * (R.refs.size() + 1)) throw std::runtime_error("leaf_geo: not 3 x (refs + 1) records");
   }
   c->bvh_depth = R.depth; c->bvh_leaves = R.leaves; c->bvh_max_leaf = R.max_leaf;
   if (R.depth > STACK_DEPTH - 1) throw std::runtime_error("BVH deeper than the traversal stack");
@@ -304,35 +304,15 @@ void upload_scene(bling_ctx* c, const bling_scene_desc* d) {
     // the 4-wide tree for the queue traversal kernels of non-fractal profiles (Traversal4)
     const bvh::Result4 Q = bvh::collapse4(R);
     const uint32_t n4 = (uint32_t)(Q.nodes.size() / 28);
-    plan_lds4(S, n4, nt, (uint32_t)R.refs.size(), (uint32_t)std::max(1, Q.stack_need), ns, kQuantBvh4 ? 64 : 112);
+    plan_lds4(S, n4, nt, (uint32_t)R.refs.size(), (uint32_t)std::max(1, Q.stack_need), ns);
     c->lds_all4 = S.lds4_nodes == n4 && S.lds4_tris == nt && S.lds4_refs == (uint32_t)R.refs.size() &&
                   S.stack4_lds == S.stack4_need && S.lds4_shapes == ns;
-    const bool quantized = kQuantBvh4 && !c->lds_all4;
     // the all-LDS kernels lay the primitives out in leaf order (dev_trace.h lds_setup<..., LEAF>)
     c->lds_trace4 = c->lds_all4 ? lds_bytes4_leaf(S.lds4_nodes, S.lds4_refs, S.stack4_lds, S.lds4_shapes)
-                                : lds_bytes4(S.lds4_nodes, S.lds4_tris, S.lds4_refs, S.stack4_lds, S.lds4_shapes, quantized);
-    // one node format per scene: float, or quantized in BLING_QBVH4 builds unless all in LDS (Traversal4)
-    if (!quantized) {
-      c->nodes4.upload(reinterpret_cast<const float4*>(Q.nodes.data()), Q.nodes.size() / 4);
-    } else {
-      const std::vector<uint32_t> qn = bvh::quantize4(Q);
-      c->nodes4.upload(reinterpret_cast<const float4*>(qn.data()), qn.size() / 4);
-    }
+                                : lds_bytes4(S.lds4_nodes, S.lds4_tris, S.lds4_refs, S.stack4_lds, S.lds4_shapes);
+    c->nodes4.upload(reinterpret_cast<const float4*>(Q.nodes.data()), Q.nodes.size() / 4);
     c->bvh4_depth = Q.depth;
     S.num_nodes4 = n4;
-    // in-line shadow test of the cornell profile's shading kernel (wavefront.h inline_shadow): the
-    // whole tree in LDS, a stack bound within the register stack (dev_trace.h occluded_lds),
-    // and an LDS copy small enough that four shading blocks (36 KiB of ring each) still share a CU.
-    // Experiment builds only (BLING_INLINE_SHADOW=1); BLING_INLINE_SHADOW=0 in the environment then
-    // turns it off (A/B measurements).
-    {
-      const char* env = std::getenv("BLING_INLINE_SHADOW");
-      const size_t bytes = lds_bytes4_leaf(n4, (uint32_t)R.refs.size(), 0u, ns);
-      const bool on = BLING_INLINE_SHADOW && !(env && env[0] == '0') && c->lds_all4 && fractal_prim < 0 &&
-                      S.stack4_need <= (uint32_t)kShadowStack && bytes <= kShadeLdsMax;
-      S.sh_inline = on ? 1u : 0u;
-      c->lds_shade = on ? bytes : 0u;
-    }
     S.stack4_lanes = 0;
     if (S.stack4_need > S.stack4_lds) {
       int cus = 256;
@@ -1127,11 +1107,11 @@ int bling_debug_scene_info(bling_ctx* c, char* buf, size_t size, size_t* len) {
   char tmp[1024];
   const int n = std::snprintf(tmp, sizeof tmp,
       "{\"prims\": %u, \"bvh_depth\": %d, \"bvh_leaves\": %d, \"bvh4_nodes\": %u, \"bvh4_depth\": %d, "
-      "\"stack4_need\": %u, \"lds_all4\": %d, \"lds_trace4\": %zu, \"pkt_n\": %u, \"bf_prims\": %u, \"sh_inline\": %u, "
-      "\"lds_shade\": %zu, \"features\": %u, \"stack4_lds\": %u, \"lds4_shapes\": %u, \"lds4_tris\": %u, "
+      "\"stack4_need\": %u, \"lds_all4\": %d, \"lds_trace4\": %zu, \"pkt_n\": %u, \"bf_prims\": %u, "
+      "\"features\": %u, \"stack4_lds\": %u, \"lds4_shapes\": %u, \"lds4_tris\": %u, "
       "\"lds4_nodes\": %u, \"max_leaf\": %d, \"sample_major\": %u}",
       c->num_prims, c->bvh_depth, c->bvh_leaves, S.num_nodes4, c->bvh4_depth, S.stack4_need, c->lds_all4 ? 1 : 0,
-      c->lds_trace4, S.pkt_n, S.bf_tris + S.bf_shapes, S.sh_inline, c->lds_shade, c->features, S.stack4_lds,
+      c->lds_trace4, S.pkt_n, S.bf_tris + S.bf_shapes, c->features, S.stack4_lds,
       S.lds4_shapes, S.lds4_tris, S.lds4_nodes, c->bvh_max_leaf, S.sample_major);
   if (n < 0) { g_err = "format error"; return BLING_EINVAL; }
   if (len) *len = (size_t)n;

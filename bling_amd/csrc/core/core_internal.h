@@ -104,7 +104,7 @@ struct bling_ctx {
   DevScene S{};
   // scene memory
   DBuf<float4> nodes, tri_geo, pkt;   // BVH2 nodes, triangle records, threaded entry list
-  DBuf<float4> leaf_geo;              // triangle records in leaf order, each with its ref (Traversal4)
+  DBuf<float4> leaf_geo;              // primitive records in leaf order, each with its ref (dev_trace.h LeafRec)
   DBuf<uint32_t> refs;
   DBuf<float> tri_normals;
   DBuf<float4> tri_frame;
@@ -164,7 +164,6 @@ struct bling_ctx {
   size_t lds_trace = 0;         // dynamic LDS bytes of the traversal kernels
   bool lds_all = false;         // the whole BVH, triangle set and leaf refs are LDS-resident
   size_t lds_trace4 = 0;        // the same for the BVH4 plan (queue traversal kernels, dev_trace.h Traversal4)
-  size_t lds_shade = 0;         // dynamic LDS of k_shade: the BVH4 copy of its in-line shadow test (or 0)
   bool lds_all4 = false;
   DBuf<float4> nodes4;          // BVH4 nodes
   DBuf<int32_t> stack4_ovf;     // BVH4 stack rows beyond the LDS ones

@@ -43,12 +43,19 @@ constexpr bool use_bvh4() { return !(F & FT_FRACTAL); }
 // conflicts per LDS instruction against 0.73, gpurun_out/r06h_sqtri36.)
 //
 // The all-LDS BVH4 kernels (ALLL: the whole tree in LDS) keep their primitives in leaf order
-// instead (`leaf`, lds_setup<..., LEAF = true>): leaf slot j of the tree's ref list holds a 48-B
-// record {v0.xyz e1.x | e1.yz e2.xy | e2.z, ref, -, -} (a shape's slot: zeros and its ref), plus one
-// zero record past the end.  A leaf's primitive test then reads its record from the slot index it
-// already holds -- the ref comes with the geometry -- instead of the ref first and the triangle one
-// dependent LDS round trip later, and a step's two tests (leaves of at most two primitives) issue
-// their loads together.  The prims of every leaf are tested in the same order as before.
+// instead (`leaf`, lds_setup<..., LEAF = true>): a copy of DevScene::leaf_geo, one 48-B record per
+// leaf slot of the tree's ref list (the layout: LeafRec below).  A leaf's primitive test then reads
+// its record from the slot index it already holds -- the ref comes with the geometry -- instead of
+// the ref first and the triangle one dependent LDS round trip later.  The prims of every leaf are
+// tested in the same order as before.
+//
+// The leaf-order record of leaf slot j, 3 float4 at index 3 j of DevScene::leaf_geo and of its LDS
+// copy: a triangle's {v0.xyz e1.x | e1.yz e2.xy | e2.z, ref, 0, 0}; a shape's slot is zeros and its
+// ref.  One zero record follows the last slot.  upload_scene (core.hip) is the one builder;
+// lds_setup<..., LEAF = true> copies its output, the tests read a, b and the first half of c.
+struct LeafRec { float4 a, b; float2 c; };      // c = (e2.z, ref)
+__host__ __device__ inline uint32_t leaf_geo_quads(uint32_t n_refs) { return 3u * (n_refs + 1u); }   // float4 of all records
+
 struct LdsScene {
   const float4* nodes; uint32_t n_nodes;
   const float4* tris; uint32_t n_tris;
@@ -66,44 +73,32 @@ __host__ __device__ inline size_t lds_bytes(uint32_t n_nodes, uint32_t n_tris, u
   return (size_t)64 * n_nodes + lds_tri_bytes(n_tris) + (size_t)16 * ((n_refs + 3) / 4) + (size_t)4 * TRACE_BLOCK * depth;
 }
 
-// LDS bytes of the BVH4 plan (Traversal4): nodes (112 B float, 64 B quantized), triangles, refs,
-// shape records, the stack rows that live in LDS.
+// LDS bytes of the BVH4 plan (Traversal4): nodes (112 B), triangles, refs, shape records, the stack
+// rows that live in LDS.
 __host__ __device__ inline size_t lds_bytes4(uint32_t n_nodes, uint32_t n_tris, uint32_t n_refs, uint32_t rows,
-                                             uint32_t n_shapes, bool quantized) {
-  return (size_t)(quantized ? 64 : 112) * n_nodes + lds_tri_bytes(n_tris) + (size_t)16 * ((n_refs + 3) / 4) + sizeof(DevShape) * n_shapes +
+                                             uint32_t n_shapes) {
+  return (size_t)112 * n_nodes + lds_tri_bytes(n_tris) + (size_t)16 * ((n_refs + 3) / 4) + sizeof(DevShape) * n_shapes +
          (size_t)4 * TRACE_BLOCK * rows;
 }
 // the same for the all-LDS kernels' LEAF layout: nodes, leaf records (refs + 1), shapes, stack rows
 // plus two spare rows (the branch-free pushes store up to two rows past the top, Traversal4::step)
 __host__ __device__ inline size_t lds_bytes4_leaf(uint32_t n_nodes, uint32_t n_refs, uint32_t rows, uint32_t n_shapes) {
-  return (size_t)112 * n_nodes + (size_t)48 * (n_refs + 1) + sizeof(DevShape) * n_shapes + (size_t)4 * TRACE_BLOCK * (rows + 2);
+  return (size_t)112 * n_nodes + (size_t)16 * leaf_geo_quads(n_refs) + sizeof(DevShape) * n_shapes + (size_t)4 * TRACE_BLOCK * (rows + 2);
 }
 
-// Copies the planned prefixes into LDS; every thread of the block must call it.  B4: the BVH4 plan;
-// QN: its nodes are the quantized ones (BLING_QBVH4 builds: every BVH4 kernel but the all-LDS one).
-template <bool B4 = false, bool QN = false, bool LEAF = false>
+// Copies the planned prefixes into LDS; every thread of the block must call it.  B4: the BVH4 plan.
+template <bool B4 = false, bool LEAF = false>
 DEV LdsScene lds_setup(const DevScene& S, float4* smem) {
-  static_assert(B4 || !QN, "only the BVH4 has quantized nodes");
-  static_assert(!LEAF || (B4 && !QN), "the leaf layout is the all-LDS float BVH4's");
+  static_assert(!LEAF || B4, "the leaf layout is the all-LDS BVH4's");
   LdsScene L;
   if constexpr (LEAF) {                          // all-LDS BVH4: nodes | leaf records | shapes | stack
     L.n_nodes = S.lds4_nodes; L.n_tris = S.lds4_tris; L.n_refs = S.lds4_refs; L.n_shapes = S.lds4_shapes;
     float4* nd = smem;
     float4* lf = nd + 7 * L.n_nodes;
     for (uint32_t q = threadIdx.x; q < 7 * L.n_nodes; q += blockDim.x) nd[q] = gen(S.nodes4[q]);
-    for (uint32_t q = threadIdx.x; q < 3 * (L.n_refs + 1); q += blockDim.x) {
-      const uint32_t j = q / 3, part = q - 3 * j;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (j < L.n_refs) {
-        const uint32_t ref = S.leaf_refs[j];
-        const bool tri = (ref >> 30) == REF_TRI;
-        const uint32_t idx = ref & 0x3FFFFFFFu;
-        if (part < 2u) { if (tri) v = gen(S.tri_geo[3 * idx + part]); }
-        else v = make_float4(tri ? gen(S.tri_geo[3 * idx + 2]).x : 0.f, __uint_as_float(ref), 0.f, 0.f);
-      }
-      lf[q] = v;
-    }
-    float4* sp = lf + 3 * (L.n_refs + 1);
+    const uint32_t nl = leaf_geo_quads(L.n_refs);            // the host's records (LeafRec), zero tail included
+    for (uint32_t q = threadIdx.x; q < nl; q += blockDim.x) lf[q] = gen(S.leaf_geo[q]);
+    float4* sp = lf + nl;
     const gptr<float4> ssrc = as_global(reinterpret_cast<const float4*>(gen(S.shapes)));
     for (uint32_t q = threadIdx.x; q < kShapeQuads * L.n_shapes; q += blockDim.x) sp[q] = gen(ssrc[q]);
     L.nodes = nd; L.leaf = lf;
@@ -116,7 +111,7 @@ DEV LdsScene lds_setup(const DevScene& S, float4* smem) {
   L.n_nodes = B4 ? S.lds4_nodes : S.lds_nodes;
   L.n_tris = B4 ? S.lds4_tris : S.lds_tris;
   L.n_refs = B4 ? S.lds4_refs : S.lds_refs;
-  constexpr uint32_t nq = QN ? 4u : (B4 ? 7u : 4u);   // float4 per node
+  constexpr uint32_t nq = B4 ? 7u : 4u;   // float4 per node
   const gptr<float4> src = B4 ? S.nodes4 : S.nodes;
   float4* nd = smem;
   float4* tr = nd + nq * L.n_nodes;
@@ -595,7 +590,7 @@ DEV bool prim_hit_ref(const DevScene& S, const LdsScene& L, uint32_t ref, const 
   }
   if (!(F & FT_FRACTAL) || kind == REF_SHAPE) {
     ++tc.shapes;
-    if ((ALLL && use_bvh4<F>()) || idx < L.n_shapes) {   // planned into LDS (BVH4 ALLL: every shape)
+    if (idx < L.n_shapes) {                               // planned into LDS
       const bool hit = shape_hit_rec<ANY, F>(L.shapes[idx], ref, r, h);
       asm volatile("" ::: "memory");                      // see the triangle loads: no merged FLAT load
       return hit;
@@ -610,32 +605,11 @@ DEV bool prim_hit_ref(const DevScene& S, const LdsScene& L, uint32_t ref, const 
   if (!ANY) { h.t = d; h.ref = ref; h.b1 = 0.f; h.b2 = 0.f; }
   return true;
 }
-// The LEAF layout's record of leaf slot j (lds_setup<..., true>) and its test: prim_hit_ref's
-// arithmetic and update rule for the ref the record carries.
-struct LeafRec { float4 a, b; float2 c; };      // c = (e2.z, ref)
-DEV LeafRec leaf_rec(const LdsScene& L, uint32_t j) {
-  LeafRec q;
-  q.a = L.leaf[3 * j]; q.b = L.leaf[3 * j + 1];
-  q.c = *reinterpret_cast<const float2*>(L.leaf + 3 * j + 2);
-  return q;
-}
-// Records j and j + 1 (contiguous) in six explicit LDS reads: left to itself the compiler splits the
-// float4 loads into ds_read2_b32 / ds_read_b96 pieces (four-cycle, 32-bank instructions).  The
-// s_waitcnt inside makes the values safe to use when the statement ends.
-DEV void leaf_rec2(const LdsScene& L, uint32_t j, LeafRec& q0, LeafRec& q1) {
-  const uint32_t addr = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float4*)(L.leaf + 3 * j);
-  asm volatile(
-      "ds_read_b128 %0, %6\n\t"
-      "ds_read_b128 %1, %6 offset:16\n\t"
-      "ds_read_b64 %2, %6 offset:32\n\t"
-      "ds_read_b128 %3, %6 offset:48\n\t"
-      "ds_read_b128 %4, %6 offset:64\n\t"
-      "ds_read_b64 %5, %6 offset:80\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(q0.a), "=&v"(q0.b), "=&v"(q0.c), "=&v"(q1.a), "=&v"(q1.b), "=&v"(q1.c)
-      : "v"(addr)
-      : "memory");
-}
+// The LEAF layout's record of leaf slot j (LeafRec) and its test: prim_hit_ref's arithmetic and
+// update rule for the ref the record carries.
+// Three explicit LDS reads: left to itself the compiler splits the float4 loads into ds_read2_b32 /
+// ds_read_b96 pieces (four-cycle, 32-bank instructions).  The s_waitcnt inside makes the values
+// safe to use when the statement ends.
 DEV LeafRec leaf_rec1(const LdsScene& L, uint32_t j) {
   LeafRec q;
   const uint32_t addr = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float4*)(L.leaf + 3 * j);
@@ -649,12 +623,6 @@ DEV LeafRec leaf_rec1(const LdsScene& L, uint32_t j) {
       : "memory");
   return q;
 }
-// 1: a step loads both records of a two-primitive leaf before the first test (leaf_rec2); 0: one
-// record before each test (fewer live registers)
-#ifndef BLING_LEAF_PAIR
-#define BLING_LEAF_PAIR 0
-#endif
-constexpr bool kLeafPair = BLING_LEAF_PAIR != 0;
 template <bool ANY, uint32_t F>
 DEV bool leaf_hit(const LdsScene& L, const LeafRec& q, const Ray& r, HitRec& h, TraceCount& tc) {
   const uint32_t ref = __float_as_uint(q.c.y);
@@ -701,9 +669,9 @@ DEV bool leaf_hit_global(const DevScene& S, const LdsScene& L, uint32_t j, const
   return hit;
 }
 
+// Leaf slot `slot` of the BVH2 plan (Traversal): the ref from LDS or global memory, then its test.
 template <bool ANY, uint32_t F, bool ALLL = false>
 DEV bool prim_hit(const DevScene& S, const LdsScene& L, uint32_t slot, const Ray& r, HitRec& h, TraceCount& tc) {
-  if constexpr (ALLL && use_bvh4<F>()) return leaf_hit<ANY, F>(L, leaf_rec(L, slot), r, h, tc);
   const uint32_t ref = (ALLL || slot < L.n_refs) ? L.refs[slot] : S.leaf_refs[slot];
   return prim_hit_ref<ANY, F, ALLL>(S, L, ref, r, h, tc);
 }
@@ -1016,50 +984,22 @@ struct Traversal {
   }
 };
 
-#ifndef BLING_QBVH4
-#define BLING_QBVH4 0
-#endif
-constexpr bool kQuantBvh4 = BLING_QBVH4 != 0;   // experiment builds only (see Traversal4)
-
-// Primitives of a leaf tested per Traversal4 step: two for the all-LDS kernel (fewer loop
-// iterations of the small, issue-bound walk: C2 closest-hit 40.2 -> 37.7 ms per pass), one with a
-// global fallback (two measured -4 % on C3; profiles/r02_ab_prim_unroll_s5.txt).
-// One ray's traversal of the 4-wide tree (DevScene::nodes4), the same resumable unit steps as
-// Traversal: a step visits one BVH4 node (four child boxes) or tests one primitive.  Hit children
-// are ordered near-first by their entry distance (five compare-exchanges), the nearest is taken and
-// the others pushed farthest-first.  Against the BVH2 this halves the dependent node fetches per ray
-// (cornell 7.6 -> ~4 visits, ducky 12.1 -> ~6), which is what the latency-bound kernels wait on.
-// The stack keeps S.stack4_lds rows in LDS; deeper rows (never on small trees: the host plans the
-// whole bound into LDS when it fits, and ALLL implies it) go to S.stack4_ovf.
-// Node format: float nodes (7 float4).  An experiment build with BLING_QBVH4=1 gives every BVH4
-// kernel but the all-LDS one quantized nodes instead (bvh::quantize4, 4 float4 = 64 B: 43 % fewer
-// bytes and load instructions per visit, 1.75x the LDS node prefix), each plane decoded with one
-// convert and one fma, bit for bit the host's bvh::dequant -- boxes that contain the float boxes, so
-// the same primitives are reached (parity green, 61 tests).  Measured on MI355X it loses: C3 5 842 ->
-// 5 656 Mrays/s (-3 %; profiles/r04_ab_session.txt r04u): the meshes traversal waits on dependent
-// node latency, not on bytes, and the decode adds issue slots to every visit.  The host uploads one
-// format per scene (core.hip upload).
+// One ray's traversal of the 4-wide tree (DevScene::nodes4, 7 float4 a node), the same resumable
+// unit steps as Traversal: a step visits one BVH4 node (four child boxes) or tests a leaf's
+// primitives.  The all-LDS kernels (ALLL) test a whole leaf, at most two primitives, per step from
+// the LDS leaf records (leaf_rec1 / leaf_hit: fewer loop iterations of the small, issue-bound walk,
+// C2 closest-hit 40.2 -> 37.7 ms per pass); the kernels with a global fallback test one primitive per
+// step from the same records in global memory (leaf_hit_global; two measured -4 % on C3,
+// profiles/r02_ab_prim_unroll_s5.txt).  Closest-hit orders the hit children near-first by their entry
+// distance (five compare-exchanges), takes the nearest and pushes the others farthest-first; any-hit
+// is order-free and pushes them unsorted.  Against the BVH2 this halves the dependent node fetches
+// per ray (cornell 7.6 -> ~4 visits, ducky 12.1 -> ~6), which is what the latency-bound kernels wait
+// on.  The stack keeps S.stack4_lds rows in LDS; deeper rows (never on small trees: the host plans
+// the whole bound into LDS when it fits, and ALLL implies it) go to S.stack4_ovf.
 // Not used by fractal profiles, whose leaf-order rule (trap T10) is written for the BVH2.
-#ifndef BLING_ANY_UNSORTED
-#define BLING_ANY_UNSORTED 1
-#endif
-constexpr bool kAnyUnsorted = BLING_ANY_UNSORTED != 0;
-#ifndef BLING_TRAV_VOTE
-#define BLING_TRAV_VOTE 0
-#endif
-constexpr bool kTravVote = BLING_TRAV_VOTE != 0;
-#ifndef BLING_PUSH_NB
-#define BLING_PUSH_NB 1
-#endif
-constexpr bool kPushNb = BLING_PUSH_NB != 0;   // all-LDS kernels: branch-free pushes (Traversal4::step)
-#ifndef BLING_LEAF_GLOBAL
-#define BLING_LEAF_GLOBAL 1
-#endif
-constexpr bool kLeafGlobal = BLING_LEAF_GLOBAL != 0;   // global-fallback kernels: leaf_hit_global
 template <bool ANY, uint32_t F, bool ALLL = false>
 struct Traversal4 {
   static constexpr int32_t NONE = 0x7FFFFFFF;
-  static constexpr int kPrimUnroll = ALLL ? 2 : 1;
   Ray r;
   V3 inv;
   HitRec h;
@@ -1086,65 +1026,23 @@ struct Traversal4 {
     if (ALLL || (uint32_t)sp < S.stack4_lds) return L.stack[sp * TRACE_BLOCK];
     return S.stack4_ovf[(size_t)((uint32_t)sp - S.stack4_lds) * S.stack4_lanes + blockIdx.x * blockDim.x + threadIdx.x];
   }
-  // four planes of one axis from their bytes: bvh::dequant, (float)q x 2^e exact, one rounding
-  DEV static float4 dequant4(uint32_t w, float s, float o) {
-    return make_float4(__builtin_fmaf((float)(w & 0xFFu), s, o), __builtin_fmaf((float)((w >> 8) & 0xFFu), s, o),
-                       __builtin_fmaf((float)((w >> 16) & 0xFFu), s, o), __builtin_fmaf((float)(w >> 24), s, o));
-  }
   DEV static void cx(float& ka, int32_t& la, float& kb, int32_t& lb) {
     const bool sw = kb < ka;
     const float k = sw ? kb : ka; kb = sw ? ka : kb; ka = k;
     const int32_t l = sw ? lb : la; lb = sw ? la : lb; la = l;
   }
   DEV bool step(const DevScene& S, const LdsScene& L, TraceCount& tc) {
-    if constexpr (ALLL && kTravVote) {
-      // experiment builds (BLING_TRAV_VOTE): one phase per iteration for the whole wave -- primitive
-      // tests when at least half of the calling lanes have some pending, else node visits
-      const bool wp = pcount > 0u;
-      const bool prim_phase = 2 * __popcll(__ballot(wp)) >= __popcll(__ballot(true));
-      if (prim_phase != wp) return false;
-      if (wp) {
-        if (prim_hit<ANY, F, ALLL>(S, L, pfirst, r, h, tc) && ANY) { h.ref = 0u; return true; }
-        ++pfirst; --pcount;
-#pragma unroll
-        for (int u = 1; u < kPrimUnroll; ++u) {
-          if (pcount > 0u) {
-            if (prim_hit<ANY, F, ALLL>(S, L, pfirst, r, h, tc) && ANY) { h.ref = 0u; return true; }
-            ++pfirst; --pcount;
-          }
-        }
-        return false;
-      }
-    }
-    if constexpr (ALLL && !kTravVote) {
+    if constexpr (ALLL) {
       if (pcount > 0u) {                         // a whole leaf (at most two primitives) per step
-        // both records' loads issue together; the second may be the zero record past the last leaf
-        // slot, and is tested only when the leaf has it
-        if constexpr (kLeafPair) {
-          LeafRec q0, q1;
-          leaf_rec2(L, pfirst, q0, q1);
-          if (leaf_hit<ANY, F>(L, q0, r, h, tc) && ANY) { h.ref = 0u; return true; }
-          if (pcount > 1u && leaf_hit<ANY, F>(L, q1, r, h, tc) && ANY) { h.ref = 0u; return true; }
-        } else {
-          if (leaf_hit<ANY, F>(L, leaf_rec1(L, pfirst), r, h, tc) && ANY) { h.ref = 0u; return true; }
-          if (pcount > 1u && leaf_hit<ANY, F>(L, leaf_rec1(L, pfirst + 1u), r, h, tc) && ANY) { h.ref = 0u; return true; }
-        }
+        // one record before each test; the second is tested only when the leaf has it
+        if (leaf_hit<ANY, F>(L, leaf_rec1(L, pfirst), r, h, tc) && ANY) { h.ref = 0u; return true; }
+        if (pcount > 1u && leaf_hit<ANY, F>(L, leaf_rec1(L, pfirst + 1u), r, h, tc) && ANY) { h.ref = 0u; return true; }
         pfirst += min(pcount, 2u); pcount -= min(pcount, 2u);
         if (pcount > 0u) return false;
       }
     } else if (pcount > 0u) {                    // "if-if": see Traversal::step
-      if (((kLeafGlobal && !ALLL) ? leaf_hit_global<ANY, F>(S, L, pfirst, r, h, tc) : prim_hit<ANY, F, ALLL>(S, L, pfirst, r, h, tc)) && ANY) {
-        h.ref = 0u;
-        return true;
-      }
+      if (leaf_hit_global<ANY, F>(S, L, pfirst, r, h, tc) && ANY) { h.ref = 0u; return true; }
       ++pfirst; --pcount;
-#pragma unroll
-      for (int u = 1; u < kPrimUnroll; ++u) {    // further primitives of the same leaf, same order
-        if (pcount > 0u) {
-          if (prim_hit<ANY, F, ALLL>(S, L, pfirst, r, h, tc) && ANY) { h.ref = 0u; return true; }
-          ++pfirst; --pcount;
-        }
-      }
       if (pcount > 0u) return false;
     }
     if (node == NONE) {
@@ -1153,31 +1051,14 @@ struct Traversal4 {
       if (node == NONE) return false;            // popped a leaf: its primitives come next
     }
     float4 lx, ly, lz, hx, hy, hz, lk;
-    if constexpr (ALLL || !kQuantBvh4) {
-      if (ALLL || (uint32_t)node < L.n_nodes) {
-        const float4* np = L.nodes + 7 * node;
-        lx = np[0]; ly = np[1]; lz = np[2]; hx = np[3]; hy = np[4]; hz = np[5]; lk = np[6];
-        asm volatile("" ::: "memory");           // see prim_hit: no merged FLAT load
-      } else {
-        const gptr<float4> np = S.nodes4 + 7 * node;
-        lx = gen(np[0]); ly = gen(np[1]); lz = gen(np[2]); hx = gen(np[3]); hy = gen(np[4]); hz = gen(np[5]); lk = gen(np[6]);
-        asm volatile("" ::: "memory");
-      }
+    if (ALLL || (uint32_t)node < L.n_nodes) {
+      const float4* np = L.nodes + 7 * node;
+      lx = np[0]; ly = np[1]; lz = np[2]; hx = np[3]; hy = np[4]; hz = np[5]; lk = np[6];
+      asm volatile("" ::: "memory");             // see prim_hit_ref: no merged FLAT load
     } else {
-      float4 qa, qb, qc;
-      if ((uint32_t)node < L.n_nodes) {
-        const float4* np = L.nodes + 4 * node;
-        qa = np[0]; qb = np[1]; qc = np[2]; lk = np[3];
-        asm volatile("" ::: "memory");
-      } else {
-        const gptr<float4> np = S.nodes4 + 4 * node;
-        qa = gen(np[0]); qb = gen(np[1]); qc = gen(np[2]); lk = gen(np[3]);
-        asm volatile("" ::: "memory");
-      }
-      // words: origin xyz, scale x | scale yz, lo bytes x y | lo bytes z, hi bytes x y z
-      lx = dequant4(__float_as_uint(qb.z), qa.w, qa.x); ly = dequant4(__float_as_uint(qb.w), qb.x, qa.y);
-      lz = dequant4(__float_as_uint(qc.x), qb.y, qa.z); hx = dequant4(__float_as_uint(qc.y), qa.w, qa.x);
-      hy = dequant4(__float_as_uint(qc.z), qb.x, qa.y); hz = dequant4(__float_as_uint(qc.w), qb.y, qa.z);
+      const gptr<float4> np = S.nodes4 + 7 * node;
+      lx = gen(np[0]); ly = gen(np[1]); lz = gen(np[2]); hx = gen(np[3]); hy = gen(np[4]); hz = gen(np[5]); lk = gen(np[6]);
+      asm volatile("" ::: "memory");
     }
     ++tc.nodes;
     const float ox = r.o.x, oy = r.o.y, oz = r.o.z, tmin = r.tmin, tmax = h.t;
@@ -1198,7 +1079,7 @@ struct Traversal4 {
       nh += hit ? 1 : 0;
     }
     if (nh == 0) { node = NONE; return false; }
-    if (ANY && kAnyUnsorted) {                   // any-hit is order-free: no near-first sort
+    if (ANY) {                                   // any-hit is order-free: no near-first sort
       int32_t first = NONE;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -1215,7 +1096,7 @@ struct Traversal4 {
     cx(key[0], lnk[0], key[2], lnk[2]);
     cx(key[1], lnk[1], key[3], lnk[3]);
     cx(key[1], lnk[1], key[2], lnk[2]);
-    if constexpr (ALLL && kPushNb) {
+    if constexpr (ALLL) {
       // the same pushes (lnk[nh - 1] .. lnk[1], farthest first) as three unconditional stores to rows
       // sp .. sp + 2 (the host plans spare rows) and one add: no branch per push
       const int32_t s0 = nh > 3 ? lnk[3] : (nh > 2 ? lnk[2] : lnk[1]);
@@ -1234,64 +1115,6 @@ struct Traversal4 {
     return false;
   }
 };
-
-// Any-hit query of one ray against the LDS copy of the whole BVH4 (lds_all4 scenes), for the shading
-// kernel's in-line shadow test (wavefront.h inline_shadow): the same padded boxes, slab arithmetic
-// and primitive tests as Traversal4<true, F, true>, with the stack in registers (a shift register of
-// kShadowStack entries, static indices only -- the host enables it only when the tree's exact stack
-// bound fits) instead of LDS rows.  Any-hit is order-free: true iff some primitive tests a hit in
-// [tmin, tmax], whatever the visiting order, so the answer is the traversal kernel's.
-constexpr int kShadowStack = 8;
-template <uint32_t F>
-DEV bool occluded_lds(const DevScene& S, const LdsScene& L, const Ray& r) {
-  const V3 inv = mk(bfast::rcp_cr(r.d.x), bfast::rcp_cr(r.d.y), bfast::rcp_cr(r.d.z));
-  HitRec h{r.tmax, REF_NONE, 0.f, 0.f};
-  TraceCount tc{0u, 0u, 0u, 0u};
-  int32_t stk[kShadowStack];
-#pragma unroll
-  for (int i = 0; i < kShadowStack; ++i) stk[i] = 0;
-  int sp = 0;
-  int32_t link = 0;                               // the root
-  for (;;) {
-    bool next = false;                            // a hit child taken directly (Traversal4's order of pushes)
-    if (link < 0) {                               // a leaf: its primitives
-      const uint32_t code = ~(uint32_t)link, first = code >> 8, cnt = code & 0xFFu;
-      for (uint32_t q = 0; q < cnt; ++q)
-        if (prim_hit<true, F, true>(S, L, first + q, r, h, tc)) return true;
-    } else {                                      // an inner node: one hit child next, the others pushed
-      const float4* np = L.nodes + 7 * link;
-      const float4 lx = np[0], ly = np[1], lz = np[2], hx = np[3], hy = np[4], hz = np[5], lk = np[6];
-      const int32_t lnk[4] = {__float_as_int(lk.x), __float_as_int(lk.y), __float_as_int(lk.z), __float_as_int(lk.w)};
-      const float blx[4] = {lx.x, lx.y, lx.z, lx.w}, bly[4] = {ly.x, ly.y, ly.z, ly.w}, blz[4] = {lz.x, lz.y, lz.z, lz.w};
-      const float bhx[4] = {hx.x, hx.y, hx.z, hx.w}, bhy[4] = {hy.x, hy.y, hy.z, hy.w}, bhz[4] = {hz.x, hz.y, hz.z, hz.w};
-      int32_t take = 0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {               // Traversal4's slab arithmetic per child
-        const float ax = (blx[k] - r.o.x) * inv.x, bx = (bhx[k] - r.o.x) * inv.x;
-        const float ay = (bly[k] - r.o.y) * inv.y, by = (bhy[k] - r.o.y) * inv.y;
-        const float az = (blz[k] - r.o.z) * inv.z, bz = (bhz[k] - r.o.z) * inv.z;
-        const float lo = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), r.tmin));
-        const float hi = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), h.t));
-        if (lo <= hi && lnk[k] != bvh4_empty) {
-          if (!next) { take = lnk[k]; next = true; }
-          else if (sp < kShadowStack) {           // never full: the host enables this for stack bounds <= 8
-#pragma unroll
-            for (int i = kShadowStack - 1; i > 0; --i) stk[i] = stk[i - 1];
-            stk[0] = lnk[k];
-            ++sp;
-          }
-        }
-      }
-      link = take;
-    }
-    if (next) continue;
-    if (sp == 0) return false;
-    link = stk[0];
-#pragma unroll
-    for (int i = 0; i < kShadowStack - 1; ++i) stk[i] = stk[i + 1];
-    --sp;
-  }
-}
 
 template <bool ANY, uint32_t F, bool ALLL>
 using QTraversal = typename std::conditional<use_bvh4<F>(), Traversal4<ANY, F, ALLL>, Traversal<ANY, F, ALLL>>::type;

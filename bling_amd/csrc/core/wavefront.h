@@ -72,7 +72,6 @@ constexpr int trace_min_waves() { return (F & FT_FRACTAL) ? 3 : ((ALLL && use_bv
 // Per-vertex flags (the .x word of the metadata record)
 constexpr uint32_t VF_SH = 1u, VF_MIS = 2u, VF_TERM = 4u;   // shadow ray / BSDF-MIS ray set up; path ends
 constexpr uint32_t VF_SPEC = 8u;                            // Path: the continuation sample was specular
-constexpr uint32_t VF_OCC = 0x200u;                         // in-line shadow test: the shadow ray is occluded
 // bits 4-8: DirectLighting depth of the next ray; bits 16-23: the light hit (intLe) + 1; bits 24-31:
 // the light sampled (sampleOneLight) -- scenes hold at most 254 lights (upload checks)
 DEV uint32_t vf_depth(uint32_t vf) { return (vf >> 4) & 31u; }
@@ -125,11 +124,11 @@ DEV Est load_est(const PathSet& P, uint32_t s, uint32_t vf, bool factored_) {
 // whatever the flags say (their slots always exist; a value whose ray was not traced is never used),
 // so every load of the record issues together with the metadata's instead of one memory latency
 // after it.  The flags still select what the resolve uses.
-DEV Est load_est_eager(const PathSet& P, uint32_t s, bool factored_, bool occ = true) {
+DEV Est load_est_eager(const PathSet& P, uint32_t s, bool factored_) {
   Est m;
   m.mdir = P.mdir[s];
   m.mhit = P.mhit[s];
-  m.occ = occ ? P.occ[s] : 0u;
+  m.occ = P.occ[s];
   m.fac = factored_ ? P.fac[s] : make_float4(0.f, 0.f, 0.f, 0.f);
   m.cf = factored_ ? P.cf[s] : make_float4(0.f, 0.f, 0.f, 0.f);
   return m;
@@ -292,30 +291,14 @@ constexpr uint32_t FEED_CHUNK = 64;
 template <bool ALLL>
 constexpr int trace_steps() { return ALLL ? 1 : 3; }
 
-// Queue-in-register refill (take_q): measured on MI355X (profiles/r05_ab_session.txt r05g) C2
-// neutral (+0.2 %), C3 -3.4 % (the meshes profile's closest kernel 78 -> 82 VGPRs, 6 -> 5 waves), so
-// experiment builds only (BLING_FEED_QREG=1)
-#ifndef BLING_FEED_QREG
-#define BLING_FEED_QREG 0
-#endif
-constexpr bool kFeedQreg = BLING_FEED_QREG != 0;
 struct WaveFeed {
   uint32_t chunk, cur, end, n, nw;
-  // queue-in-register mode (init with a queue): lane l holds entry l of the current chunk (qv) and of
-  // the wave's next chunk (qn, loaded one chunk ahead), so a refill reads its entry with one lane
-  // shuffle instead of a dependent global load before the ray's own loads
-  const uint32_t* q = nullptr;
-  uint32_t qv = 0u, qn = 0u;
-  DEV uint32_t chunk_entry(uint32_t c) const {
-    const uint64_t i = (uint64_t)c * FEED_CHUNK + (threadIdx.x & 63u);
-    return i < n ? q[i] : 0u;
-  }
+  const uint32_t* q = nullptr;                    // the queue whose entries take_q reads (or none)
   DEV void init(uint32_t n_, const uint32_t* queue = nullptr) {
     n = n_;
     nw = gridDim.x * (blockDim.x >> 6);
     chunk = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     q = queue;
-    if (kFeedQreg && q) { qv = chunk_entry(chunk); qn = chunk_entry(chunk + nw); }
     open();
   }
   DEV void open() {
@@ -323,33 +306,10 @@ struct WaveFeed {
     cur = c0 < n ? (uint32_t)c0 : n;
     end = (uint32_t)((uint64_t)cur + FEED_CHUNK < n ? cur + FEED_CHUNK : n);
   }
-  // take() in queue-in-register mode: *v = the queue entry q[*e]
+  // take() of a feed with a queue: *v = the queue entry q[*e]
   DEV bool take_q(bool live, uint32_t* e, uint32_t* v) {
-    if constexpr (!kFeedQreg) {                   // experiment builds: the entry loaded per refill
-      const bool got = take(live, e);
-      if (got) *v = q[*e];
-      return got;
-    }
-    bool got = false;
-    const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-      const bool want = !live && !got;
-      const unsigned long long m = __ballot(want);
-      if (m == 0ull || cur >= end) break;
-      const uint32_t avail = end - cur;
-      const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      const uint32_t val = (uint32_t)__shfl((int)qv, (int)((cur + rank) & (FEED_CHUNK - 1u)), 64);
-      if (want && rank < avail) { *e = cur + rank; *v = val; got = true; }
-      const uint32_t used = min((uint32_t)__popcll(m), avail);
-      cur += used;
-      if (cur == end) {
-        chunk += nw;
-        open();
-        qv = qn;
-        if (cur < end) qn = chunk_entry(chunk + nw);
-      }
-    }
+    const bool got = take(live, e);
+    if (got) *v = q[*e];
     return got;
   }
   // Free lanes (live == false) receive consecutive entries; returns true for a lane that got entry *e.
@@ -399,7 +359,7 @@ static __global__ __launch_bounds__(256) TRACE_OCC void k_trace_closest(const De
                                                                  Counters* __restrict__ C) {
   extern __shared__ float4 smem[];
   const DevScene& S = *Sptr;
-  const LdsScene L = lds_setup<use_bvh4<F>(), use_bvh4<F>() && !ALLL && kQuantBvh4, ALLL && use_bvh4<F>()>(S, smem);
+  const LdsScene L = lds_setup<use_bvh4<F>(), ALLL && use_bvh4<F>()>(S, smem);
   const uint32_t n = *(volatile uint32_t*)&W.qcount[Q_CLOSEST];
   const uint32_t* q = W.queue[Q_CLOSEST];
   WaveFeed feed;
@@ -435,7 +395,7 @@ static __global__ __launch_bounds__(256) TRACE_OCC void k_trace_any(const DevSce
                                                    Counters* __restrict__ C) {
   extern __shared__ float4 smem[];
   const DevScene& S = *Sptr;
-  const LdsScene L = lds_setup<use_bvh4<F>(), use_bvh4<F>() && !ALLL && kQuantBvh4, ALLL && use_bvh4<F>()>(S, smem);
+  const LdsScene L = lds_setup<use_bvh4<F>(), ALLL && use_bvh4<F>()>(S, smem);
   const uint32_t n = *(volatile uint32_t*)&W.qcount[Q_ANY];
   const uint32_t* q = W.queue[Q_ANY];
   WaveFeed feed;
@@ -823,25 +783,6 @@ static __global__ __launch_bounds__(256) void k_trace_any_bf(const DevScene* __r
 template <uint32_t F>
 constexpr bool factored() { return (F & ~(FT_MATTE | FT_AREA | FT_TRIS)) == 0; }
 
-// In-line shadow test (the cornell profile, DevScene::sh_inline scenes: the whole BVH4, triangles,
-// refs and shapes in LDS and a stack bound that fits dev_trace.h's register stack).  The shading
-// lane that sets up the light sample's shadow ray tests it itself against the block's LDS copy of
-// the tree (occluded_lds) and keeps the answer in the vertex flags (VF_OCC), instead of storing the
-// ray (32 B) for k_trace_any, which then does not run, and reading its 4-B answer back.  The answer
-// is the same: any-hit is order-free.  The check order of sampleLightMis (lpdf, Li, f, occluded;
-// Scene.hs:61-69) is kept: the ray is tested only when the other three passed.  Its query still
-// counts as a shadow ray (QF_ANY).
-// Measured on MI355X and left out of the product build (BLING_INLINE_SHADOW=1 experiment builds
-// only; profiles/r05_ab_session.txt): on C2 the in-line walk cost k_shade as much as the any-hit
-// launch it replaces (shade 49.7 -> 58.4 ms per pass, k_trace_any's ~9 ms gone, 9 487 -> 9 516
-// Mrays/s) -- the walk runs at k_shade's four waves without lane refill -- and compiling it in
-// raised k_shade's scratch (88 -> 136 B) even with the test switched off.
-#ifndef BLING_INLINE_SHADOW
-#define BLING_INLINE_SHADOW 0
-#endif
-template <uint32_t F>
-constexpr bool inline_shadow() { return BLING_INLINE_SHADOW && F == (FT_MATTE | FT_AREA | FT_TRIS); }
-
 // the factored lobe's spectrum from its byte offset in S.textures (~0u = white)
 DEV const float* lobe_r(const DevScene& S, uint32_t off) {
 #if defined(BLING_SCENE_LOAD_EXPERIMENT)                              // measurement-only builds
@@ -857,7 +798,7 @@ DEV const float* lobe_r(const DevScene& S, uint32_t off) {
 template <uint32_t F>
 DEV void direct_setup(const DevScene& S, const WaveState& W, const PathSet& O, uint32_t o, const SampleKey& k,
                       const Bsdf& bsdf, V3 wo, V3 p, float eps, int dl1, int dl2, int db1, int db2, uint32_t& vf,
-                      bool& app_mis, bool& app_sh, Est& m, uint32_t sid, int dvd = -1, Ray* shr = nullptr) {
+                      bool& app_mis, bool& app_sh, Est& m, uint32_t sid, int dvd = -1) {
   (void)W; (void)sid;
   int lc = S.num_lights;
   if (lc > 0) {
@@ -892,11 +833,8 @@ DEV void direct_setup(const DevScene& S, const WaveState& W, const PathSet& O, u
           const float w = smp.delta ? 1.f : power_heuristic(smp.pdf, bsdf_pdf<F>(bsdf, wo, smp.wi));
           wpdf = w / smp.pdf; fs1 = s1; fs2 = s2;
           const float stmin = kd_root(S, smp.ray) ? smp.ray.tmin : INFINITY;   // +inf: rejected (kd_root)
-          if (shr) { *shr = smp.ray; shr->tmin = stmin; }           // tested by the caller (inline_shadow)
-          else {
-            O.sh_o[o] = make_float4(smp.ray.o.x, smp.ray.o.y, smp.ray.o.z, stmin);
-            O.sh_d[o] = make_float4(smp.ray.d.x, smp.ray.d.y, smp.ray.d.z, smp.ray.tmax);
-          }
+          O.sh_o[o] = make_float4(smp.ray.o.x, smp.ray.o.y, smp.ray.o.z, stmin);
+          O.sh_d[o] = make_float4(smp.ray.d.x, smp.ray.d.y, smp.ray.d.z, smp.ray.tmax);
           vf |= VF_SH;
           app_sh = true;
         }
@@ -1086,7 +1024,7 @@ DEV Sp next_throughput(const DevScene& S, const PathSet& P, uint32_t s, const fl
 template <uint32_t F>
 DEV uint32_t shade_vertex(const DevScene& S, const WaveState& W, const PathSet& O, uint32_t o, int depth, uint32_t seed,
                           uint32_t pass, float ty, uint32_t vfin, float4 hv, const Ray& ray, uint32_t pix,
-                          uint32_t nid, uint32_t sid, const LdsScene* Lsh = nullptr) {
+                          uint32_t nid, uint32_t sid) {
   const bool spec = (vfin & VF_SPEC) != 0;
   bool app_sh = false, app_mis = false, app_cont = false;
   SampleKey k = sample_key(seed, pass, pix, nid);
@@ -1144,14 +1082,10 @@ DEV uint32_t shade_vertex(const DevScene& S, const WaveState& W, const PathSet& 
   O.org[o] = make_float4(p.x, p.y, p.z, eps);
   // the continuation ray Ray p wi eps infinity (Path.hs:79) with its kd_root flag (dev_trace.h)
   O.dir[o] = make_float4(cwi.x, cwi.y, cwi.z, kd_flag_w(pc, !cont || kd_root(S, Ray{p, cwi, eps, INFINITY})));
-  Ray shr{mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 1.f), 0.f, 0.f};
   direct_setup<F>(S, W, O, o, k, bsdf, wo, p, eps, 1 + 4 * depth, 1 + 3 * depth, 2 + 4 * depth, 2 + 3 * depth, vf,
-                  app_mis, app_sh, m, sid, depth, Lsh ? &shr : nullptr);
+                  app_mis, app_sh, m, sid, depth);
   O.mdir[o] = m.mdir;
   if constexpr (factored<F>()) O.fac[o] = m.fac;
-  if constexpr (inline_shadow<F>()) {
-    if (Lsh && app_sh && occluded_lds<F>(S, *Lsh, shr)) vf |= VF_OCC;      // sampleLightMis's `occluded`
-  }
   O.meta[o] = make_uint4(vf, pix, nid, sid);
   // what the next launches need of the vertex: cf (factored: the continuation's factors and the
   // lobe offset the candidates use), the origin of the continuation / MIS rays, the continuation
@@ -1163,8 +1097,8 @@ DEV uint32_t shade_vertex(const DevScene& S, const WaveState& W, const PathSet& 
   SBW(W, SB_MDIR, 16, app_mis);
   SBW(W, SB_FAC, 16, factored<F>() && (app_sh || app_mis));
   SBW(W, SB_META, 16, true);
-  SBW(W, SB_SHO, 16, app_sh && !Lsh);
-  SBW(W, SB_SHD, 16, app_sh && !Lsh);
+  SBW(W, SB_SHO, 16, app_sh);
+  SBW(W, SB_SHD, 16, app_sh);
   SBW(W, SB_LSC, 64, !factored<F>() && app_sh);
   SBW(W, SB_BSC, 64, !factored<F>() && app_mis);
   return QF_RESOLVE | (app_sh ? QF_ANY : 0u) | (app_mis ? QF_MIS : 0u) | (app_cont ? QF_CONT : 0u);
@@ -1207,14 +1141,6 @@ static __global__ __launch_bounds__(256) SHADE_OCC void k_shade(const DevScene* 
   const uint32_t n = *(volatile uint32_t*)&W.qcount[qin];
   const uint32_t* q = W.queue[qin];
   unsigned long long n_drop = 0;
-  // in-line shadow test: the block's LDS copy of the whole BVH4 (dynamic LDS behind the ring)
-  LdsScene Lsh{nullptr, 0u, nullptr, 0u, nullptr, nullptr, 0u, nullptr, nullptr, 0u};
-  bool inl = false;
-  if constexpr (inline_shadow<F>()) {
-    extern __shared__ float4 smem[];
-    inl = S.sh_inline != 0u;
-    if (inl) Lsh = lds_setup<true, false, true>(S, smem);
-  }
   // the ring hands a vertex's slot, entry, hit and metadata records and sY(T) from the resolve phase
   // to the shading lane, so the shading phase loads only the ray (org, dir) from the path set
   __shared__ uint32_t ring_e[4][SHADE_RING];
@@ -1233,7 +1159,7 @@ static __global__ __launch_bounds__(256) SHADE_OCC void k_shade(const DevScene* 
     const uint4 meta = ring_m[wv][slot];
     const Ray ray{mk(ro.x, ro.y, ro.z), mk(rdv.x, rdv.y, rdv.z), ro.w, INFINITY};
     W.qflag[e] = (uint8_t)shade_vertex<F>(S, W, W.nxt, e, depth, seed, pass, ring_y[wv][slot], meta.x, hv, ray, meta.y,
-                                          meta.z, meta.w, inl ? &Lsh : nullptr);
+                                          meta.z, meta.w);
   };
   // the next chunk's queue entry is loaded one iteration ahead (its latency overlaps this chunk)
   uint32_t qnext = 0u;
@@ -1282,17 +1208,12 @@ static __global__ __launch_bounds__(256) SHADE_OCC void k_shade(const DevScene* 
         m.cf = make_float4(0.f, 0.f, 0.f, 0.f);
         Sp Tp = sconst(1.f);                                                  // T(d - 1)
         if constexpr (FUSED) {
-#if defined(BLING_LAZY_EST)                                           // experiment builds only
-          m = load_est(W.cur, s, meta.x, factored<F>());
-#else
-          m = load_est_eager(W.cur, s, factored<F>(), !inl);
-#endif
-          if (inl) m.occ = (meta.x & VF_OCC) ? 1u : 0u;                  // tested in line at d - 1
+          m = load_est_eager(W.cur, s, factored<F>());
           if (depth > 1) Tp = load_sp(W.cur.T, s);
           L = resolve_L<F>(S, W, s, meta.x, m, Tp, depth == 1, meta.w, depth - 1, ro);
           SBR(W, SB_MDIR, 16, (meta.x & VF_MIS) != 0u);
           SBR(W, SB_MHIT, 8, (meta.x & VF_MIS) != 0u);
-          SBR(W, SB_OCC, 4, !inl && (meta.x & VF_SH) != 0u);
+          SBR(W, SB_OCC, 4, (meta.x & VF_SH) != 0u);
           SBR(W, SB_FAC, 16, factored<F>() && (meta.x & (VF_SH | VF_MIS)) != 0u);
           SBR(W, SB_T, 64, depth > 1);
           SBR(W, SB_L, 64, depth > 1);
