@@ -6,12 +6,14 @@
 #   oracle/_build/liboracle.so        CPU oracle (test infrastructure)     (g++ + OpenMP)
 #   bling_amd/_lib/bling              C++ command-line renderer (host front end)
 #   bling_amd/_lib/libbling_mathcheck.so  exhaustive device check of common/fast_cr.h (tests)
+#   tests/ref/_build/liblt_ref.so     CPU restatement of the light tracer over the oracle (tests)
 
 HIPCC    ?= /opt/rocm/bin/hipcc
 CXX      ?= g++
 ARCH     ?= gfx950
 LIBDIR   := bling_amd/_lib
 ORADIR   := oracle/_build
+LTRDIR   := tests/ref/_build
 space    := $(subst ,, )
 
 HOST_SRC := bling_amd/csrc/host/loader.cpp
@@ -41,11 +43,12 @@ HIPFLAGS  := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -ffp-contract=off -fno-
              -Wno-unused-result -munsafe-fp-atomics
 
 all: $(LIBDIR)/libbling_host.so $(LIBDIR)/libbling_hip.so $(ORADIR)/liboracle.so $(LIBDIR)/bling \
-     $(LIBDIR)/libbling_mathcheck.so
+     $(LIBDIR)/libbling_mathcheck.so $(LTRDIR)/liblt_ref.so
 
 host: $(LIBDIR)/libbling_host.so
 oracle: $(ORADIR)/liboracle.so
 core: $(LIBDIR)/libbling_hip.so
+ltref: $(LTRDIR)/liblt_ref.so
 
 $(LIBDIR)/libbling_host.so: $(HOST_SRC) $(HOST_HDR)
 	@mkdir -p $(LIBDIR)
@@ -54,6 +57,11 @@ $(LIBDIR)/libbling_host.so: $(HOST_SRC) $(HOST_HDR)
 $(ORADIR)/liboracle.so: $(ORA_SRC) $(ORA_HDR)
 	@mkdir -p $(ORADIR)
 	$(CXX) $(HOSTFLAGS) -fopenmp -shared -o $@ $(ORA_SRC)
+
+# the light tracer's restatement includes oracle/oracle.cpp (its internals are file-local); tests only
+$(LTRDIR)/liblt_ref.so: tests/ref/lighttracer_ref.cpp $(ORA_SRC) $(ORA_HDR)
+	@mkdir -p $(LTRDIR)
+	$(CXX) $(HOSTFLAGS) -Wno-subobject-linkage -fopenmp -shared -o $@ tests/ref/lighttracer_ref.cpp
 
 # one object per unit (core, sppm driver, one per kernel feature profile) so make -j compiles the
 # kernel instantiations in parallel
@@ -82,6 +90,6 @@ variant: $(CORE_OBJ)
 	$(HIPCC) $(HIPFLAGS) -shared -o $(LIBDIR)/libbling_hip_$(V).so $(CORE_OBJ)
 
 clean:
-	rm -rf $(LIBDIR) $(ORADIR) build
+	rm -rf $(LIBDIR) $(ORADIR) $(LTRDIR) build
 
-.PHONY: all host oracle core clean variant
+.PHONY: all host oracle core ltref clean variant

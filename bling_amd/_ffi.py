@@ -62,6 +62,26 @@ class SppmStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LightStats(C.Structure):
+    """bling_light_stats (include/bling.h)."""
+    _fields_ = [("photons", C.c_uint64), ("photon_rays", C.c_uint64), ("shadow_rays", C.c_uint64),
+                ("splats", C.c_uint64), ("dropped", C.c_uint64), ("ms_total", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class LightRecord(C.Structure):
+    """bling_light_record (include/bling.h): one splat of the light tracer's record mode, 32 bytes."""
+    _fields_ = [("photon", C.c_uint32), ("depth", C.c_uint32), ("sx", C.c_int32), ("sy", C.c_int32),
+                ("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("pad", C.c_uint32)]
+
+
+class LightTracer(C.Structure):
+    """bling_light_tracer (include/bling_scene.h): the trailing member of bling_scene_desc."""
+    _fields_ = [("pass_photons", C.c_int32), ("pixel_area", C.c_float), ("w2r", C.c_float * 16)]
+
+
 class RenderConfig(C.Structure):
     _fields_ = [("renderer", C.c_int32), ("sampler", C.c_int32), ("nu", C.c_int32), ("nv", C.c_int32),
                 ("spp", C.c_int32), ("max_depth", C.c_int32), ("sample_depth", C.c_int32),
@@ -91,6 +111,8 @@ def host() -> C.CDLL:
         lib.bling_host_counts.argtypes = [C.c_void_p, c_u32p]
         lib.bling_host_last_error.restype = C.c_char_p
         lib.bling_host_film_to_rgb.argtypes = [c_f32p, C.c_int, C.c_int, c_f32p]
+        lib.bling_host_film_splat_to_rgb.argtypes = [c_f32p, c_f32p, C.c_float, C.c_int, C.c_int, c_f32p]
+        lib.bling_host_light.argtypes = [C.c_void_p, C.POINTER(LightTracer)]
         lib.bling_host_write_hdr.argtypes = [C.c_char_p, c_f32p, C.c_int, C.c_int]
         lib.bling_host_write_hdr.restype = C.c_int
         lib.bling_host_rgb_pixels.argtypes = [c_f32p, C.c_int, C.c_int, C.POINTER(C.c_uint8)]
@@ -103,7 +125,8 @@ def host() -> C.CDLL:
 HIP_SYMBOLS = ["bling_create", "bling_scene_upload", "bling_scene_validate", "bling_render_pass", "bling_render_pass_device",
                "bling_trace", "bling_trace_device", "bling_sample_li", "bling_sample_li_vertices", "bling_pass_tile_layout",
                "bling_film_add_tiles", "bling_film_add_shards", "bling_sppm_pass", "bling_sppm_pixel_stats", "bling_sppm_reset",
-               "bling_render", "bling_debug_stream_bytes", "bling_debug_scene_info", "bling_debug_sppm_hitpoints", "bling_debug_sppm_buckets", "bling_destroy", "bling_last_error", "bling_version"]
+               "bling_render", "bling_debug_stream_bytes", "bling_debug_scene_info", "bling_debug_sppm_hitpoints", "bling_debug_sppm_buckets",
+               "bling_light_pass", "bling_debug_light_records", "bling_destroy", "bling_last_error", "bling_version"]
 
 
 class Progress(C.Structure):
@@ -167,6 +190,11 @@ def hip() -> C.CDLL:
         lib.bling_debug_sppm_buckets.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), c_f32p,
                                                  C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         lib.bling_debug_sppm_buckets.restype = C.c_int
+        lib.bling_light_pass.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, c_f32p, C.POINTER(LightStats)]
+        lib.bling_light_pass.restype = C.c_int
+        lib.bling_debug_light_records.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  C.POINTER(LightRecord), C.c_size_t, C.POINTER(C.c_size_t)]
+        lib.bling_debug_light_records.restype = C.c_int
         lib.bling_debug_scene_info.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
         lib.bling_debug_scene_info.restype = C.c_int
         if hasattr(lib, "bling_debug_stream_bytes"):

@@ -96,6 +96,8 @@ void validate_scene(const bling_scene_desc* d) {
     if (d->config.max_depth < 1 || d->config.max_depth > SPPM_MAX_DEPTH)
       throw std::invalid_argument("sppm maxDepth outside [1, " + std::to_string(SPPM_MAX_DEPTH) + "]");
     if (d->config.sppm_photons < 1 || d->config.sppm_threads < 1) throw std::invalid_argument("bad sppm photon count");
+  } else if (d->config.renderer == BLING_RENDERER_LIGHT) {
+    if (d->light.pass_photons < 1) throw std::invalid_argument("light tracer passPhotons < 1");
   } else if (d->config.spp <= 0) {
     throw std::invalid_argument("bad render config");
   } else if (d->config.integrator == BLING_INTEGRATOR_DIRECT) {
@@ -437,6 +439,8 @@ void upload_scene(bling_ctx* c, const bling_scene_desc* d) {
   S.images = as_global(c->images.p);
   S.num_lights = (int32_t)d->num_lights;
   S.camera = d->camera;
+  std::memcpy(S.lt_w2r, d->light.w2r, sizeof S.lt_w2r);
+  S.lt_pixel_area = d->light.pixel_area;
   std::memcpy(S.filter_table, d->filter.table, sizeof S.filter_table);
   S.filter_w = d->filter.width; S.filter_h = d->filter.height;
   const bling_render_config& cfg = d->config;
@@ -466,7 +470,9 @@ void upload_scene(bling_ctx* c, const bling_scene_desc* d) {
   c->dscene.upload(&S, 1);
   c->film_dev.free();
   c->cfg = cfg;
+  c->lt = d->light;
   c->sppm.free_all();
+  c->light.free_all();
 }
 
 int run_wave(bling_ctx* c, const WaveState& W, uint32_t n, uint32_t seed, uint32_t pass, bool stats,
@@ -1268,6 +1274,72 @@ int bling_sppm_reset(bling_ctx* c) {
     if (!c) throw std::invalid_argument("null argument");
     HIPCHK(hipSetDevice(c->device));
     c->sppm.free_all();
+    return BLING_OK;
+  });
+}
+
+// ---- light tracer (light_tracer.h, light_pass.hip)
+static int light_ready(bling_ctx* c) {
+  if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
+  if (c->cfg.renderer != BLING_RENDERER_LIGHT) throw std::invalid_argument("the uploaded scene's renderer is not the light tracer");
+  if (!c->peers.empty()) throw std::invalid_argument("the light tracer runs on a single-device context");
+  if (c->S.camera.kind != BLING_CAM_PERSPECTIVE) {
+    g_err = "light tracer: an environment camera cannot be sampled (sampleCam, Camera.hs:102)";
+    return BLING_EUNSUPPORTED;
+  }
+  if (c->features & FT_PROCTEX) {
+    g_err = "light tracer: blend / gradient / checker / cellNoise textures are not supported by the light tracer";
+    return BLING_EUNSUPPORTED;
+  }
+  return BLING_OK;
+}
+
+static uint32_t light_launch(bling_ctx* c, uint32_t seed, uint32_t pass, uint32_t first, uint32_t count, bool splat,
+                             uint32_t rec_cap, bling_light_stats* st) {
+  if ((c->features & ~kProfiles[0]) == 0u) return light_pass_t<kProfiles[0]>(c, seed, pass, first, count, splat, rec_cap, st);
+  return light_pass_t<kSppmAll>(c, seed, pass, first, count, splat, rec_cap, st);
+}
+
+int bling_light_pass(bling_ctx* c, uint32_t seed, uint32_t pass_index, float* splat_inout, bling_light_stats* st) {
+  return guarded([&] {
+    if (!c) throw std::invalid_argument("null argument");
+    if (int rc = light_ready(c)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    LightState& P = c->light;
+    const size_t ns = (size_t)c->S.width * c->S.height * 3;
+    if (P.splat.n != ns) P.splat.alloc(ns);
+    if (splat_inout) HIPCHK(hipMemcpy(P.splat.p, splat_inout, ns * sizeof(float), hipMemcpyHostToDevice));
+    else HIPCHK(hipMemset(P.splat.p, 0, ns * sizeof(float)));
+    if (st) std::memset(st, 0, sizeof *st);
+    light_launch(c, seed, pass_index, 0u, (uint32_t)c->lt.pass_photons, true, 0u, st);
+    if (splat_inout) HIPCHK(hipMemcpy(splat_inout, P.splat.p, ns * sizeof(float), hipMemcpyDeviceToHost));
+    return BLING_OK;
+  });
+}
+
+int bling_debug_light_records(bling_ctx* c, uint32_t seed, uint32_t pass_index, uint32_t first_photon, uint32_t n_photons,
+                              bling_light_record* records, size_t cap, size_t* n) {
+  return guarded([&] {
+    if (!c || !n || (cap && !records)) throw std::invalid_argument("null argument");
+    *n = 0;
+    if (int rc = light_ready(c)) return rc;
+    if ((uint64_t)first_photon + n_photons > (uint64_t)c->lt.pass_photons) throw std::invalid_argument("photon range beyond passPhotons");
+    if (cap > 0x7FFFFFFFull) throw std::invalid_argument("record capacity too large");
+    if (n_photons == 0) return BLING_OK;
+    HIPCHK(hipSetDevice(c->device));
+    // a launch needs a buffer to claim slots in: one record at least, so the count is always known
+    const uint32_t rcap = (uint32_t)std::max<size_t>(cap, 1);
+    const uint32_t got = light_launch(c, seed, pass_index, first_photon, n_photons, false, rcap, nullptr);
+    *n = got;
+    if (got > cap) {
+      g_err = "light records: " + std::to_string(got) + " records exceed the capacity " + std::to_string(cap);
+      return BLING_EINVAL;
+    }
+    static_assert(sizeof(bling_light_record) == 2 * sizeof(uint4), "record layout");
+    if (got) HIPCHK(hipMemcpy(records, c->light.rec.p, (size_t)got * sizeof(bling_light_record), hipMemcpyDeviceToHost));
+    std::sort(records, records + got, [](const bling_light_record& a, const bling_light_record& b) {
+      return a.photon != b.photon ? a.photon < b.photon : a.depth < b.depth;
+    });
     return BLING_OK;
   });
 }

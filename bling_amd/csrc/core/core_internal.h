@@ -19,6 +19,7 @@
 #include "bvh_build.h"
 #include "wavefront.h"
 #include "sppm.h"
+#include "light_tracer.h"
 
 namespace bcore {
 using namespace bd;
@@ -88,6 +89,15 @@ struct SppmState {
     hp_key.free(); grid.free(); ctr.free(); tiles.free();
     ready = false; hp_cap = items_cap = 0;
   }
+};
+
+// Light tracer state (light_tracer.h): the splat image, counters and the record buffer of record mode
+struct LightState {
+  DBuf<float> splat;
+  DBuf<unsigned long long> ctr;
+  DBuf<uint4> rec;
+  DBuf<uint32_t> rec_count;
+  void free_all() { splat.free(); ctr.free(); rec.free(); rec_count.free(); }
 };
 
 }  // namespace bcore
@@ -169,6 +179,8 @@ struct bling_ctx {
   DBuf<int32_t> stack4_ovf;     // BVH4 stack rows beyond the LDS ones
   bling_render_config cfg{};    // the uploaded scene's renderer configuration
   SppmState sppm;
+  LightState light;
+  bling_light_tracer lt{};      // the uploaded scene's light tracer block (photons per pass)
   // Multi-device fan-out (bling_create with n_devices > 1): one context per further device; every
   // device renders its share as tile images, the peers push theirs over xGMI into stage, and the
   // primary adds them all (Rendering.hs:118).
@@ -324,5 +336,11 @@ void launch_trace_prof(bling_ctx* c, const float* rays, uint32_t n, int any_hit,
 template <uint32_t F>
 void sppm_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, bling_sppm_stats* st);
 void sppm_init(bling_ctx* c);
+// One light tracer launch (light_pass.hip): photons first .. first + count - 1 of the pass into the
+// context's splat image (splat = true) and / or its record buffer of rec_cap records (0 = off);
+// returns the records claimed, which may exceed rec_cap.
+template <uint32_t F>
+uint32_t light_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, uint32_t first, uint32_t count, bool splat,
+                      uint32_t rec_cap, bling_light_stats* st);
 
 }  // namespace bcore

@@ -173,6 +173,9 @@ struct DevScene {
   // that union itself: the reference tests every query against it first (kdTreePrimitive's
   // intersectAABB b r, KdTree.hs:236-244), and a ray it rejects misses the scene (dev_trace.h kd_root)
   float kd_lo[3], kd_hi[3];
+  // light tracer (light_tracer.h sample_cam): mkProjective's world-to-raster matrix and pixel area
+  // as the loader formed them (bling_scene_desc.light)
+  float lt_w2r[16], lt_pixel_area;
 };
 
 }  // namespace bd

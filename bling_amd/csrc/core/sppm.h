@@ -19,7 +19,14 @@
 namespace bd {
 
 constexpr uint32_t DIM_SPPM_1D = 0x100000u, DIM_SPPM_2D = 0x200000u, SPPM_PHOTON_PIXEL = 0x80000000u;
-constexpr int SPPM_MAX_DEPTH = 16;               // eye-tree depth bound (one parked sibling per level)
+// Light tracer (light_tracer.h): photon i of a pass draws from pixel_key(seed, pass, LT_PIXEL | i >> 16),
+// sample_key(pk, i & 0xFFFF) -- a pixel tag neither a camera pixel (< 2^30) nor SPPM_PHOTON_PIXEL | k
+// reaches -- and only fresh dimensions: 1D DIM_FRESH1D + dim with ul = 0 and at vertex d ubc = 1 + 2 d,
+// roulette = 2 + 2 d; 2D DIM_FRESH2D + 2 dim (+ 1) with ulo = 0, uld = 1 and at vertex d ubd = 2 + d.
+constexpr uint32_t LT_PIXEL = 0x40000000u;
+constexpr uint32_t LT_DIM_UL = 0u, LT_DIM_UBC = 1u, LT_DIM_ROULETTE = 2u;      // 1D
+constexpr uint32_t LT_DIM_ULO = 0u, LT_DIM_ULD = 1u, LT_DIM_UBD = 2u;          // 2D
+constexpr int SPPM_MAX_DEPTH = 16;              // eye-tree depth bound (one parked sibling per level)
 constexpr int SPPM_PHOTON_BOUNCES = 1 << 16;     // exit bound of the (unbounded) photon walk
 
 struct SppmGrid { float lo[3]; float scale; float r2max; uint32_t cnt; uint32_t items; uint32_t pad; };

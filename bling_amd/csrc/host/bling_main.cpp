@@ -39,6 +39,30 @@ int main(int argc, char** argv) {
   }
   int w = d->config.width, h = d->config.height;
   std::vector<float> film((size_t)w * h * 4, 0.f), rgb((size_t)w * h * 3);
+  if (d->config.renderer == BLING_RENDERER_LIGHT) {
+    // instance Renderer LightTracer (Renderer/LightTracer.hs:37-52): the film stays empty, every pass
+    // adds its splats, and the image of pass n weighs them with 1 / (n * passPhotons)
+    std::vector<float> splat((size_t)w * h * 3, 0.f);
+    for (int p = 1; p <= passes; ++p) {
+      bling_light_stats st;
+      if (bling_light_pass(ctx, 0x0B11A6u, (uint32_t)p, splat.data(), &st) != 0) { std::fprintf(stderr, "%s\n", bling_last_error()); return 1; }
+      std::printf("pass %d: %.1f ms, %llu photons, %llu splats, %.1f Mrays/s\n", p, st.ms_total, (unsigned long long)st.photons,
+                  (unsigned long long)st.splats, (st.photon_rays + st.shadow_rays) / (st.ms_total * 1e3));
+      const float sw = 1.f / (float)((long long)p * d->light.pass_photons);
+      char name[512];
+      std::snprintf(name, sizeof name, "%s-%05d", out, p);
+      std::printf("Writing %s...\n", name);
+      bling_host_film_splat_to_rgb(film.data(), splat.data(), sw, w, h, rgb.data());
+      if (bling_host_write_png_splat((std::string(name) + ".png").c_str(), film.data(), splat.data(), sw, w, h) != 0 ||
+          bling_host_write_hdr((std::string(name) + ".hdr").c_str(), rgb.data(), w, h) != 0) {
+        std::fprintf(stderr, "%s\n", bling_host_last_error());
+        return 1;
+      }
+    }
+    bling_destroy(ctx);
+    bling_host_free(hs);
+    return 0;
+  }
   for (int p = 1; p <= passes; ++p) {
     bling_pass_params pp{0x0B11A6u, (uint32_t)p, 0, 1, 1, 0};
     bling_stats st;

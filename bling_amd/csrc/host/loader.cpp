@@ -269,6 +269,7 @@ struct Overrides {
   bool filter = false; int fkind = 0; float fp[5] = {0, 0, 0, 0, 0};
   bool sppm = false; int sp_photons = 0, sp_md = 0; float sp_radius = 0.f, sp_alpha = 0.8f;
   int sppm_threads = 0;
+  bool light = false; int lt_photons = 0;
 };
 
 struct Mat { bling_material m; };
@@ -285,6 +286,7 @@ struct Builder {
   bling_render_config cfg{};
   bling_filter filter{};
   bling_camera camera{};
+  bling_light_tracer lt{};
   Xf xf = identityX();
   int material = 0;
   bool has_emit = false;
@@ -397,6 +399,13 @@ struct Builder {
     Xf s2r = cat(t, cat(st2, st1));       // t <> st2 <> st1 (infixr)
     Xf r2s = inverseX(s2r);
     Xf r2c = cat(r2s, inverseX(p));
+    // sampleCam's world-to-raster transform and pixel area, in mkProjective's order (Camera.hs:128-133)
+    Xf w2s = cat(inverseX(c2w), p);
+    Xf w2r = cat(w2s, s2r);
+    float fl = std::tan(radians(fov) / 2.f);                                     // focal length (:147)
+    float pw = fl * (s1 - s0) / sx, ph = fl * (s3 - s2) / sy;
+    std::memcpy(lt.w2r, w2r.m.m, 64);
+    lt.pixel_area = pw * ph;
     camera.kind = BLING_CAM_PERSPECTIVE;
     std::memcpy(camera.c2w, c2w.m.m, 64); std::memcpy(camera.c2w_inv, c2w.inv.m, 64);
     std::memcpy(camera.r2c, r2c.m.m, 64); std::memcpy(camera.r2c_inv, r2c.inv.m, 64);
@@ -1178,8 +1187,11 @@ struct Parser {
         B.cfg.sppm_radius = named_float("radius");
         B.cfg.sppm_alpha = L.is_word("alpha") ? named_float("alpha") : 0.8f;   // option 0.8
         B.cfg.renderer = BLING_RENDERER_SPPM;
+      } else if (t == "light") {                      // RendererParser.hs:28-30: passPhotons comes first
+        B.lt.pass_photons = named_int("passPhotons");
+        B.cfg.renderer = BLING_RENDERER_LIGHT;
       } else {
-        // metropolis / light: not served (trap T1); skip its arguments
+        // metropolis: not served (trap T1); skip its arguments
         B.cfg.renderer = BLING_RENDERER_OTHER;
         while (L.peekc() != '}') { if (L.peek_number()) L.flt(); else L.word(); }
       }
@@ -1207,6 +1219,7 @@ struct Parser {
         B.make_camera(B.xf, lr, fd, fov, (float)B.resX, (float)B.resY);   // reads resX/resY NOW (T2)
       } else if (t == "environment") {
         B.camera.kind = BLING_CAM_ENVIRONMENT;
+        std::memset(B.lt.w2r, 0, sizeof B.lt.w2r); B.lt.pixel_area = 0.f;   // sampleCam is `error` (Camera.hs:102)
         std::memcpy(B.camera.c2w, B.xf.m.m, 64); std::memcpy(B.camera.c2w_inv, B.xf.inv.m, 64);
         B.camera.xres = (float)B.resX; B.camera.yres = (float)B.resY;
       } else L.fail("unknown camera " + t);
@@ -1266,6 +1279,7 @@ Overrides parse_overrides(const char* s) {
       o.sppm = true; o.sp_photons = I(0); o.sp_md = I(1); o.sp_radius = Fv(2);
       o.sp_alpha = parts.size() > 3 ? Fv(3) : 0.8f;
     }
+    else if (k == "light") { o.light = true; o.lt_photons = I(0); }      // light=passPhotons
     else if (k == "sppm_threads") { o.sppm_threads = I(0); if (o.sppm_threads < 1) throw ParseError("bad override " + kv); }
     else if (k == "filter") {
       o.filter = true;
@@ -1320,6 +1334,7 @@ int bling_host_load(const char* path, const char* overrides, bling_host_scene** 
       B.cfg.renderer = BLING_RENDERER_SPPM; B.cfg.sppm_photons = B.ov.sp_photons; B.cfg.max_depth = B.ov.sp_md;
       B.cfg.sppm_radius = B.ov.sp_radius; B.cfg.sppm_alpha = B.ov.sp_alpha;
     }
+    if (B.ov.light) { B.cfg.renderer = BLING_RENDERER_LIGHT; B.lt.pass_photons = B.ov.lt_photons; }
     // numCapabilities of the modelled reference run (SPPM.hs:449, 474): photons per pass are
     // threads * sn^2; 8 = this build machine's core count unless overridden
     B.cfg.sppm_threads = B.ov.sppm_threads > 0 ? B.ov.sppm_threads : 8;
@@ -1378,6 +1393,7 @@ int bling_host_load(const char* path, const char* overrides, bling_host_scene** 
     for (size_t k = 0; k < B.images.size(); ++k) B.images[k].texels = B.image_data[k].data();
     d.num_images = (uint32_t)B.images.size();
     d.images = B.images.data();
+    d.light = B.lt;
     // the infinite lights' Dist2D arrays live in the parsed LightRec objects
     for (size_t k = 0; k < B.lights.size(); ++k) {
       if (B.lights[k].kind != BLING_LIGHT_INFINITE) continue;
@@ -1388,7 +1404,7 @@ int bling_host_load(const char* path, const char* overrides, bling_host_scene** 
     sm << "image " << B.resX << "x" << B.resY << ", prims " << d.num_prims << " (triangles "
        << d.num_triangles << ", shapes " << d.num_shapes << ", fractal " << d.fractal.present << "), lights "
        << d.num_lights << ", materials " << d.num_materials << ", renderer "
-       << (B.cfg.renderer != BLING_RENDERER_SAMPLER_PATH ? "other" : B.cfg.integrator == BLING_INTEGRATOR_DIRECT ? "direct" : "path")
+       << (B.cfg.renderer == BLING_RENDERER_LIGHT ? "light" : B.cfg.renderer != BLING_RENDERER_SAMPLER_PATH ? "other" : B.cfg.integrator == BLING_INTEGRATOR_DIRECT ? "direct" : "path")
        << " md=" << B.cfg.max_depth
        << " sd=" << B.cfg.sample_depth << " sampler "
        << (B.cfg.sampler == BLING_SAMPLER_STRATIFIED ? "stratified " : "random ") << B.cfg.nu << "x"
@@ -1405,6 +1421,7 @@ int bling_host_load(const char* path, const char* overrides, bling_host_scene** 
 
 const bling_scene_desc* bling_host_desc(const bling_host_scene* s) { return s ? &s->b.desc : nullptr; }
 void bling_host_config(const bling_host_scene* s, bling_render_config* out) { *out = s->b.desc.config; }
+void bling_host_light(const bling_host_scene* s, bling_light_tracer* out) { *out = s->b.desc.light; }
 void bling_host_filter_size(const bling_host_scene* s, float* wh) { wh[0] = s->b.desc.filter.width; wh[1] = s->b.desc.filter.height; }
 void bling_host_filter_table(const bling_host_scene* s, float* out256) {
   std::memcpy(out256, s->b.desc.filter.table, sizeof s->b.desc.filter.table);

@@ -21,6 +21,11 @@ from .scene import Job
 DEFAULT_SEED = 0x0B11A6   # master seed of the benchmark
 
 
+# numpy view of bling_light_record (include/bling.h)
+LIGHT_RECORD = np.dtype([("photon", "<u4"), ("depth", "<u4"), ("sx", "<i4"), ("sy", "<i4"),
+                         ("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("pad", "<u4")])
+
+
 class BlingError(RuntimeError):
     def __init__(self, rc: int, msg: str):
         super().__init__(f"bling error {rc}: {msg}")
@@ -268,6 +273,34 @@ class Context:
     def sppm_reset(self):
         _check(_ffi.hip().bling_sppm_reset(self._h))
 
+    def light_pass(self, seed=DEFAULT_SEED, pass_index=1, splat: np.ndarray | None = None):
+        """One light tracer pass (Renderer/LightTracer.hs:41-52) into a host splat image (X,Y,Z),
+        accumulated.  Returns (splat, LightStats)."""
+        job = self.job
+        if splat is None:
+            splat = np.zeros(job.width * job.height * 3, np.float32)
+        st = _ffi.LightStats()
+        _check(_ffi.hip().bling_light_pass(self._h, seed, pass_index, _ffi.f32ptr(splat), C.byref(st)))
+        return splat, st
+
+    def light_records(self, seed=DEFAULT_SEED, pass_index=1, first_photon=0, n_photons=None, cap=None):
+        """bling_debug_light_records: the splats of a range of the pass's photons as a structured
+        array (photon, depth, sx, sy, x, y, z, pad), sorted by (photon, depth).  Without cap the
+        buffer is sized by a first counting call; a given cap that is too small raises."""
+        if n_photons is None:
+            n_photons = self.job.light.pass_photons - first_photon
+        lib = _ffi.hip()
+        n = C.c_size_t()
+        if cap is None:
+            rc = lib.bling_debug_light_records(self._h, seed, pass_index, first_photon, n_photons, None, 0, C.byref(n))
+            if rc != 0 and n.value == 0:
+                _check(rc)
+            cap = n.value
+        rec = np.zeros(cap, LIGHT_RECORD)
+        _check(lib.bling_debug_light_records(self._h, seed, pass_index, first_photon, n_photons,
+                                             rec.ctypes.data_as(C.POINTER(_ffi.LightRecord)), cap, C.byref(n)))
+        return rec[:n.value]
+
     def close(self):
         if self._h:
             _ffi.hip().bling_destroy(self._h)
@@ -339,9 +372,43 @@ class SPPMRenderer:
         return film, splat
 
 
+class LightTracerRenderer:
+    """``instance Renderer LightTracer`` (Renderer/LightTracer.hs:37-52) on the MI355X core: passes
+    1, 2, ... until the reporter returns False; each PassDone carries the (empty) film, the
+    accumulated splat image and the splat weight 1 / (pass * passPhotons) of `PassDone n img'` (:50)."""
+
+    def __init__(self, device: int = 0, seed: int = DEFAULT_SEED):
+        self.device = device
+        self.seed = seed
+
+    def render(self, job: Job, report):
+        ppp = job.light.pass_photons
+        ctx = Context(self.device)
+        ctx.upload(job)
+        film = np.zeros(job.width * job.height * 4, np.float32)
+        splat = np.zeros(job.width * job.height * 3, np.float32)
+        report(Progress("Started"))
+        p = 1
+        while True:
+            splat, st = ctx.light_pass(seed=self.seed, pass_index=p, splat=splat)
+            info = st.as_dict()
+            info["splat"] = splat
+            info["splat_weight"] = 1.0 / (p * ppp)
+            if not report(Progress("PassDone", p, film, info)):
+                break
+            p += 1
+        ctx.close()
+        return film, splat
+
+
+RENDERER_LIGHT = 3   # BLING_RENDERER_LIGHT (include/bling_scene.h)
+
+
 def render(job: Job, passes: int = 1, device: int = 0, seed: int = DEFAULT_SEED) -> np.ndarray:
     """Render `passes` progressive passes (the commented bling CLI harness renders exactly one,
-    src/cmdline/Main.hs:15-26)."""
+    src/cmdline/Main.hs:15-26).  A sampler job returns its film (W, X, Y, Z); a `light` job, which
+    only splats, returns the RGB image (h, w, 3) of its accumulated splats with the weight
+    1 / (passes * passPhotons)."""
     count = {"n": 0}
 
     def rep(pr: Progress) -> bool:
@@ -350,4 +417,9 @@ def render(job: Job, passes: int = 1, device: int = 0, seed: int = DEFAULT_SEED)
             return count["n"] < passes
         return True
 
+    if job.config.renderer == RENDERER_LIGHT:
+        from .scene import film_splat_to_rgb
+        film, splat = LightTracerRenderer(device, seed).render(job, rep)
+        sw = np.float32(1.0) / np.float32(count["n"] * job.light.pass_photons)
+        return film_splat_to_rgb(film, splat, sw, job.width, job.height)
     return SamplerRenderer(device, seed).render(job, rep)

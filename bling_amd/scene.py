@@ -83,6 +83,9 @@ class Job:
         cfg = _ffi.RenderConfig()
         lib.bling_host_config(h, C.byref(cfg))
         self.config = cfg
+        lt = _ffi.LightTracer()
+        lib.bling_host_light(h, C.byref(lt))
+        self.light = lt                     # passPhotons, w2r, pixel_area (bling_light_tracer)
         fw = np.zeros(2, np.float32)
         lib.bling_host_filter_size(h, _ffi.f32ptr(fw))
         self.filter_size = (float(fw[0]), float(fw[1]))
@@ -181,6 +184,19 @@ def film_to_rgb(film: np.ndarray, w: int, h: int) -> np.ndarray:
     film = np.ascontiguousarray(film, np.float32).reshape(-1)
     out = np.zeros(w * h * 3, np.float32)
     _ffi.host().bling_host_film_to_rgb(_ffi.f32ptr(film), w, h, _ffi.f32ptr(out))
+    return out.reshape(h, w, 3)
+
+
+def film_splat_to_rgb(film: np.ndarray | None, splat: np.ndarray, sw: float, w: int, h: int) -> np.ndarray:
+    """getPixel with a splat image and its weight sw, then xyzToRgb (Image.hs:301-314); film None =
+    the empty film of a renderer that only splats (the light tracer)."""
+    if film is None:
+        film = np.zeros(w * h * 4, np.float32)
+    film = np.ascontiguousarray(film, np.float32).reshape(-1)
+    splat = np.ascontiguousarray(splat, np.float32).reshape(-1)
+    out = np.zeros(w * h * 3, np.float32)
+    _ffi.host().bling_host_film_splat_to_rgb(_ffi.f32ptr(film), _ffi.f32ptr(splat), float(np.float32(sw)), w, h,
+                                             _ffi.f32ptr(out))
     return out.reshape(h, w, 3)
 
 

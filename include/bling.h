@@ -100,8 +100,8 @@ typedef struct bling_stats {
  * as tile images (BLING_PASS_TILE_IMAGES), every peer pushes its images over xGMI onto
  * device_ids[0] (concurrent copies, one per peer stream), and they are added there (addTile) once
  * every device has succeeded, before the call returns.  bling_trace, bling_sample_li and the SPPM
- * calls run on device_ids[0] only.  One process per GPU (torch.distributed / RCCL) instead passes
- * one id per process and uses the shard fields.  A device id listed twice is BLING_EINVAL (unless
+ * calls run on device_ids[0] only (the light tracer refuses such a context).  One process per GPU
+ * (torch.distributed / RCCL) instead passes one id per process and uses the shard fields.  A device id listed twice is BLING_EINVAL (unless
  * the environment sets BLING_ALLOW_REPEATED_DEVICES=1, a test hook that runs the fan-out with two
  * contexts on one GPU). */
 int bling_create(const int* device_ids, int n_devices, bling_ctx** out);
@@ -258,6 +258,45 @@ int bling_debug_sppm_hitpoints(bling_ctx* ctx, float* pos_r2, uint64_t* keys, si
  * mr at pivot positions (*ni entries).  Arrays are copied only when their capacity suffices. */
 int bling_debug_sppm_buckets(bling_ctx* ctx, uint32_t* bstart, uint32_t* items, float* mr, size_t cap_b,
                              size_t cap_i, size_t* nb, size_t* ni);
+
+/* ---- light tracer (Renderer/LightTracer.hs), the third consumer of the trace core ---- */
+typedef struct bling_light_stats {
+    uint64_t photons;          /* photons emitted: passPhotons                                   */
+    uint64_t photon_rays;      /* closest-hit queries of photon segments (oneRay / nextVertex)    */
+    uint64_t shadow_rays;      /* any-hit queries of camera connections (connectCam's occluded)   */
+    uint64_t splats;           /* connections handed to splatSample inside the image, finite      */
+    uint64_t dropped;          /* NaN / Inf connections inside the image, skipped (Image.hs:201-221) */
+    double   ms_total;         /* device time of the pass (HIP events)                           */
+} bling_light_stats;
+
+/* Replaces: one pass of `instance Renderer LightTracer` (Renderer/LightTracer.hs:37-52) for a scene
+ * whose renderer block is `light passPhotons N`: N photons leave the lights (oneRay, :54-66), and
+ * every vertex of a photon's walk (nextVertex, :84-109; no depth limit, Russian roulette with 0.8
+ * beyond depth 3) is connected to the pinhole of the perspective camera (connectCam, :68-82;
+ * sampleCam, Camera.hs:90-100) and splatted (splatSample) into splat_inout: W*H*3 XYZ, host,
+ * ACCUMULATED into, may be NULL.  pass_index numbers passes from 1.  The reference's image after
+ * pass k is getPixel of an empty film with splat weight sw = 1 / (k * passPhotons) (:50).
+ * As in the reference, a vertex behind the camera is projected and splatted all the same, the lens
+ * radius is ignored, and the emitter itself and specular chains seen from the eye never appear
+ * (traps).  Errors: BLING_ENOSCENE without a scene; BLING_EINVAL when the scene's
+ * renderer is not the light tracer or the context holds several devices; BLING_EUNSUPPORTED for an
+ * environment camera (sampleCam is `error` there) and for computed textures (as bling_sppm_pass). */
+int bling_light_pass(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, float* splat_inout,
+                     bling_light_stats* stats);
+
+/* Parity hook: the splats of photons first_photon .. first_photon + n_photons - 1 of that pass, one
+ * record per splat, sorted by (photon, depth); nothing is accumulated.  The film's float atomics
+ * make its sums order-dependent; the records are what parity is pinned on.  *n receives the number
+ * of records the photons produced; at most cap are written.  A capacity smaller than *n is
+ * BLING_EINVAL (with *n set, so the caller can size the buffer): never a silent truncation. */
+typedef struct bling_light_record {
+    uint32_t photon, depth;    /* photon index of the pass, vertex depth (0 = first hit)          */
+    int32_t  sx, sy;           /* pixel (floor of the raster position)                            */
+    float    x, y, z;          /* the XYZ the splat adds                                          */
+    uint32_t pad;
+} bling_light_record;
+int bling_debug_light_records(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, uint32_t first_photon,
+                              uint32_t n_photons, bling_light_record* records, size_t cap, size_t* n);
 
 /* Diagnostics (no reference counterpart): the path-state bytes the shading kernel k_shade moved in
  * the context's last bling_render_pass*, per stream and direction -- out[2 k] read, out[2 k + 1]

@@ -237,8 +237,9 @@ typedef struct bling_filter {
 enum bling_sampler_kind { BLING_SAMPLER_STRATIFIED = 0, BLING_SAMPLER_RANDOM = 1 };
 enum bling_renderer_kind {
     BLING_RENDERER_SAMPLER_PATH = 0,   /* sampler renderer (Rendering.hs:77-78) + surface integrator      */
-    BLING_RENDERER_OTHER = 1,          /* metropolis / light tracer: not served                            */
-    BLING_RENDERER_SPPM = 2            /* sppm photonCount maxDepth radius [alpha] (RendererParser.hs:40-45) */
+    BLING_RENDERER_OTHER = 1,          /* metropolis: not served                                           */
+    BLING_RENDERER_SPPM = 2,           /* sppm photonCount maxDepth radius [alpha] (RendererParser.hs:40-45) */
+    BLING_RENDERER_LIGHT = 3           /* light passPhotons N (RendererParser.hs:47-50, Renderer/LightTracer.hs) */
 };
 /* the sampler renderer's surface integrator (IO/IntegratorParser.hs:15-47) */
 enum bling_integrator_kind {
@@ -261,6 +262,17 @@ typedef struct bling_render_config {
     int32_t sppm_threads;      /* numCapabilities of the reference run: photons per pass are
                                   threads * sn^2, sn = max 1 (ceiling (sqrt (n / threads)))    */
 } bling_render_config;
+
+/* ---- light tracer (Renderer/LightTracer.hs; sampleCam, Camera.hs:90-100) ----
+ * The camera connection needs mkProjective's world-to-raster transform and pixel area
+ * (Camera.hs:118-133) as the reference forms them: w2r = (inverse c2w <> p) <> s2r and
+ * ap = pw * ph.  Neither can be rebuilt bit for bit from the camera's stored r2c / c2w inverses,
+ * so the loader forms both.  They describe the perspective camera (zero for an environment one). */
+typedef struct bling_light_tracer {
+    int32_t pass_photons;      /* passPhotons: photons per pass (BLING_RENDERER_LIGHT only)     */
+    float   pixel_area;        /* ap = pw * ph                                                 */
+    float   w2r[16];           /* world -> raster, row-major                                   */
+} bling_light_tracer;
 
 typedef struct bling_scene_desc {
     /* triangles (TriangleMesh.hs:39-60; vertices already transformed to world space) */
@@ -301,6 +313,9 @@ typedef struct bling_scene_desc {
     /* texture images (BLING_TEX_IMAGE / BLING_STEX_IMAGE) */
     uint32_t           num_images;
     const bling_image* images;
+
+    /* trailing member: everything above keeps its offset */
+    bling_light_tracer light;
 } bling_scene_desc;
 
 #ifdef __cplusplus
