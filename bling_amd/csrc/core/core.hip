@@ -358,6 +358,15 @@ void upload_scene(bling_ctx* c, const bling_scene_desc* d) {
     std::memcpy(sh[k].o2w, s.o2w, 64);
   }
   c->shapes.upload(sh.data(), ns);
+  // The MIS cull (wavefront.h mis_cull_test) tests the sampled area light's own shape only: it holds
+  // when no other shape carries that light.  The loader pairs them one to one; a hand-made
+  // description that does not renders without the cull.
+  c->mis_cull_ok = true;
+  for (uint32_t k = 0; k < ns; ++k) {
+    const int l = d->shapes[k].light;
+    if (l >= 0 && !((uint32_t)l < d->num_lights && d->lights[l].kind == BLING_LIGHT_AREA && d->lights[l].shape == (int)k))
+      c->mis_cull_ok = false;
+  }
   c->materials.upload(d->materials, d->num_materials);
   c->textures.upload(d->textures, d->num_textures);
   c->stex.upload(d->scalar_textures, d->num_scalar_textures);
@@ -572,6 +581,7 @@ int render(bling_ctx* c, const bling_pass_params* p, float* film_dev, bling_stat
   c->ensure_paths((uint32_t)std::min<uint64_t>(chunk, std::max<uint64_t>(total, 1)));
   chunk = std::min<uint32_t>(chunk, c->cap);
   WaveState P = c->state();
+  if (p->flags & BLING_PASS_NO_MIS_CULL) P.mis_cull = 0u;
   hipStream_t s = c->stream;
   HIPCHK(hipMemsetAsync(c->counters.p, 0, sizeof(Counters), s));
   hipEvent_t e0, e1;
@@ -637,6 +647,7 @@ int render(bling_ctx* c, const bling_pass_params* p, float* film_dev, bling_stat
   Counters hc;
   HIPCHK(hipMemcpy(&hc, c->counters.p, sizeof hc, hipMemcpyDeviceToHost));
   std::memcpy(c->stream_bytes, hc.sb, sizeof c->stream_bytes);
+  c->mis_culled = hc.mis_culled;
   if (st) {
     std::memset(st, 0, sizeof *st);
     st->camera_samples = samples;
@@ -1122,6 +1133,21 @@ int bling_debug_scene_info(bling_ctx* c, char* buf, size_t size, size_t* len) {
   if (n < 0) { g_err = "format error"; return BLING_EINVAL; }
   if (len) *len = (size_t)n;
   if (buf && size) { std::strncpy(buf, tmp, size - 1); buf[size - 1] = '\0'; }
+  return BLING_OK;
+}
+
+int bling_debug_set_mis_cull(bling_ctx* c, int on) {
+  if (!c) { g_err = "null argument"; return BLING_EINVAL; }
+  c->mis_cull_off = !on;
+  for (auto& p : c->peers) p->mis_cull_off = !on;
+  return BLING_OK;
+}
+
+int bling_debug_mis_culled(bling_ctx* c, uint64_t* out) {
+  if (!c || !out) { g_err = "null argument"; return BLING_EINVAL; }
+  uint64_t n = c->mis_culled;
+  for (const auto& p : c->peers) n += p->mis_culled;
+  *out = n;
   return BLING_OK;
 }
 

@@ -161,6 +161,10 @@ struct bling_ctx {
   DBuf<uint8_t> qflag;
   DBuf<TileDesc> tiles_dev;
   DBuf<Counters> counters;
+  uint64_t mis_culled = 0;      // Counters::mis_culled of the last pass (bling_debug_mis_culled)
+  // every shape that carries an area light is that light's own shape (wavefront.h mis_cull_test)
+  bool mis_cull_ok = false;
+  bool mis_cull_off = false;    // bling_debug_set_mis_cull(ctx, 0): bling_sample_li walks every MIS ray too
   uint64_t stream_bytes[2 * BLING_N_STREAMS] = {};   // Counters::sb of the last pass (BLING_STREAM_STATS)
   DBuf<DevScene> dscene;      // the DevScene record in device memory (kernels take a pointer)
   DBuf<float> film_dev;
@@ -224,9 +228,9 @@ struct bling_ctx {
     result.alloc(cap); img.alloc(cap);
     qmem.alloc((size_t)6 * cap);     // SHADE0, SHADE1, CLOSEST (2 cap), ANY, RESOLVE
     march.alloc((size_t)2 * cap);    // reused: closest-queue results, then any-queue results
-    qcount.alloc(Q_N);
+    qcount.alloc(QC_N);              // the Q_N queue lengths and the culled MIS count (QC_MISCULL)
     qflag.alloc(cap);
-    blk.alloc((size_t)4 * (cap / COMPACT_CHUNK + 2));
+    blk.alloc((size_t)5 * (cap / COMPACT_CHUNK + 2));   // [nb][4], totals [4], culled [nb]
   }
   WaveState state() {
     WaveState W{};
@@ -248,6 +252,7 @@ struct bling_ctx {
     W.blk = blk.p;
     W.sb = counters.p ? counters.p->sb : nullptr;
     W.cap = cap;
+    W.mis_cull = (mis_cull_ok && !mis_cull_off) ? 1u : 0u;   // bling_render_pass* clears it on BLING_PASS_NO_MIS_CULL
     return W;
   }
 };

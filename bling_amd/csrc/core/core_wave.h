@@ -189,7 +189,7 @@ int run_wave_t(bling_ctx* c, WaveState W, uint32_t n, uint32_t seed, uint32_t pa
     }
     std::swap(W.cur, W.nxt);           // the queues built next index the set just written
     if (depth < c->S.max_depth) {      // shade at maxDepth finalises every path: nothing to queue
-      k_compact_count<<<nb, 256, 0, s>>>(W, qin);
+      k_compact_count<<<nb, 256, 0, s>>>(W, nb, qin);
       k_compact_scan<<<1, 1024, 0, s>>>(W, nb, qin, 1);
       k_compact_scatter<<<nb, 256, 0, s>>>(W, nb, qin, 1);
       launches += 3;
@@ -233,12 +233,17 @@ int run_wave_dl_t(bling_ctx* c, WaveState W, uint32_t n, uint32_t seed, uint32_t
       W.nxt = W.cur;
       launches += 2;
     }
-    if (live == 0) break;
+    if (live == 0) {
+      // the last step's MIS and shadow rays were traced above: account them (no path is alive, so
+      // k_stage adds no continuation ray and no vertex)
+      if (step > 0) k_stage<<<1, 64, 0, s>>>(W.qcount, step & 1, step, C, 0);
+      break;
+    }
     if (step >= max_steps) throw std::runtime_error("directLighting walk did not terminate");
     const int qin = step & 1;
     k_stage<<<1, 64, 0, s>>>(W.qcount, qin, step, C, 0);
     shade_dl_launch<F>(gs, s, d, W, qin, seed, pass, C);
-    k_compact_count<<<nb, 256, 0, s>>>(W, qin);
+    k_compact_count<<<nb, 256, 0, s>>>(W, nb, qin);
     k_compact_scan<<<1, 1024, 0, s>>>(W, nb, qin, 0);
     k_compact_scatter<<<nb, 256, 0, s>>>(W, nb, qin, 0);
     launches += 5;

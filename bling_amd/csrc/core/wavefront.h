@@ -158,6 +158,8 @@ struct WaveState {
   float4* dl_T;       // [levels * cap][4] weight of the pending ray
   uint32_t* dl_mask;  // bit j set = slot j pending
   uint32_t cap;
+  uint32_t mis_cull;  // 1: direct_setup answers BSDF-MIS queries that cannot reach the sampled area light
+                      // itself (mis_cull_test); 0: BLING_PASS_NO_MIS_CULL, every MIS ray is walked
 };
 
 // Per-vertex debug records (BLING_DEBUG_VERTEX builds, `make variant V=dbg`): BLING_DV_FIELDS floats
@@ -175,12 +177,18 @@ struct WaveState {
 #define DVREC3(W, i, d, f, v) do { DVREC(W, i, d, f, (v).x); DVREC(W, i, d, (f) + 1, (v).y); DVREC(W, i, d, (f) + 2, (v).z); } while (0)
 
 // Queue membership bits emitted by k_shade for entry e of its input queue.
-constexpr uint32_t QF_RESOLVE = 1u, QF_ANY = 2u, QF_MIS = 4u, QF_CONT = 8u;
+// QF_MISCULL: the vertex's BSDF-MIS query was answered by direct_setup (mis_cull_test): counted as a
+// MIS ray (k_stage), never queued.
+constexpr uint32_t QF_RESOLVE = 1u, QF_ANY = 2u, QF_MIS = 4u, QF_CONT = 8u, QF_MISCULL = 16u;
+constexpr int QF_COUNTS = 5;               // flag bits the compaction counts; the first four are scattered
+// qcount[QC_MISCULL]: culled MIS queries of the last compaction (beside the Q_N queue lengths)
+constexpr int QC_MISCULL = 5, QC_N = 6;
 constexpr uint32_t COMPACT_CHUNK = 4096;   // shade-queue entries per compaction block (4 waves x 1024)
 
 struct Counters {
   unsigned long long cam, cont, mis, shadow, dropped, node_visits, tri_tests, shape_tests, vertices, march_ticks;
   unsigned long long c_node_visits, c_tri_tests, c_shape_tests, c_march_ticks;   // closest-hit kernel only
+  unsigned long long mis_culled;           // of mis: answered by direct_setup, not walked (bling_debug_mis_culled)
   unsigned long long sb[2 * BLING_N_STREAMS];   // BLING_STREAM_STATS: k_shade's bytes per stream (read, write)
 };
 
@@ -795,10 +803,42 @@ DEV const float* lobe_r(const DevScene& S, uint32_t off) {
 // ray (1D db1 + 2D db2) and the light-sample shadow ray (2D dl2) with their candidate contributions
 // into set O at slot o; the next shade launch completes the estimate once both rays are traced.
 // m[] is the estimate record being assembled (written by the caller).
+//
+// The MIS cull.  When the sampled light Lt is an area light, resolve_L takes something from the MIS
+// ray only if its closest hit is Lt's own shape (hs.light == ln; the loader gives every area light
+// one shape, core.hip upload checks it): a miss adds light_le = black, another primitive nothing.
+// That shape can be the closest hit only if its own test accepts the ray, and the walks test a shape
+// with shape_hit_rec<false, F> and nothing else (Traversal / Traversal4 through prim_hit_ref, leaf_hit
+// and leaf_hit_global, packet_walk through prim_hit_ref, brute_walk directly), with tmax = their
+// closest t so far <= infinity.  quad_test, sphere_test, disk_test, cylinder_test and box_test use
+// tmax only to reject on t > tmax, so a ray that shape_hit_rec rejects at tmax = infinity is rejected
+// in every walk, whatever the order, ties and NaNs included (the same record, the same operations,
+// no contraction).  Such a vertex gets no MIS ray: its candidate would be exactly zero.  The finite
+// guards keep the one case where the walked ray's zero is not one: a miss multiplies the candidate
+// by black and by the weight, which gives NaN (a dropped sample) for a non-finite candidate or a
+// bpdf whose square leaves binary32's range.
+// BLING_DEBUG_VERTEX builds record every vertex's MIS hit distance (record 29): no cull there.
+template <uint32_t F>
+DEV bool mis_cull_test(const DevScene& S, const WaveState& W, const bling_light& Lt, V3 p, V3 wi, float eps,
+                       float bpdf, bool finite_f) {
+#if BLING_DEBUG_VERTEX
+  (void)S; (void)W; (void)Lt; (void)p; (void)wi; (void)eps; (void)bpdf; (void)finite_f;
+  return false;
+#else
+  if (!W.mis_cull) return false;
+  if ((F & FT_DELTA) && Lt.kind >= BLING_LIGHT_POINT) return false;
+  if (!(!(F & FT_INF) || Lt.kind == BLING_LIGHT_AREA)) return false;
+  const float b2 = bpdf * bpdf;
+  if (!(finite_f && b2 > 0.f && b2 < INFINITY)) return false;
+  HitRec h{INFINITY, REF_NONE, 0.f, 0.f};
+  return !shape_hit_rec<false, F>(light_shape<F>(S, Lt), REF_NONE, Ray{p, wi, eps, INFINITY}, h);
+#endif
+}
+
 template <uint32_t F>
 DEV void direct_setup(const DevScene& S, const WaveState& W, const PathSet& O, uint32_t o, const SampleKey& k,
                       const Bsdf& bsdf, V3 wo, V3 p, float eps, int dl1, int dl2, int db1, int db2, uint32_t& vf,
-                      bool& app_mis, bool& app_sh, Est& m, uint32_t sid, int dvd = -1) {
+                      bool& app_mis, bool& app_sh, bool& mis_culled, Est& m, uint32_t sid, int dvd = -1) {
   (void)W; (void)sid;
   int lc = S.num_lights;
   if (lc > 0) {
@@ -814,7 +854,9 @@ DEV void direct_setup(const DevScene& S, const WaveState& W, const PathSet& O, u
         float s; V3 bwi;
         const float bpdf = sample_bsdf_diffuse1<F>(bsdf, wo, lb1, lb2, s, bwi);
         DVREC3(W, sid, dvd, 18, bwi); DVREC(W, sid, dvd, 21, bpdf);
-        if (!(bpdf == 0.f) && !is_black(diffuse1_f(r, s))) {
+        const bool cand = !(bpdf == 0.f) && !is_black(diffuse1_f(r, s));
+        mis_culled = cand && mis_cull_test<F>(S, W, Lt, p, bwi, eps, bpdf, fabsf(s) < INFINITY);
+        if (cand && !mis_culled) {
           const float lpdf = light_pdf<F>(S, Lt, p, bwi);
           m.mdir = make_float4(bwi.x, bwi.y, bwi.z,               // the MIS ray Ray p wi eps infinity
                                kd_flag_w(power_heuristic(bpdf, lpdf), kd_root(S, Ray{p, bwi, eps, INFINITY})));
@@ -849,7 +891,9 @@ DEV void direct_setup(const DevScene& S, const WaveState& W, const PathSet& O, u
       Sp bf; V3 bwi; int bfl;
       float bpdf = sample_bsdf<F>(bsdf, wo, lBc, lb1, lb2, bf, bwi, bfl);
       DVREC3(W, sid, dvd, 18, bwi); DVREC(W, sid, dvd, 21, bpdf);
-      if (!(bpdf == 0.f) && !is_black(bf)) {
+      const bool cand = !(bpdf == 0.f) && !is_black(bf);
+      mis_culled = cand && mis_cull_test<F>(S, W, Lt, p, bwi, eps, bpdf, !s_bad(bf));
+      if (cand && !mis_culled) {
         float lpdf = light_pdf<F>(S, Lt, p, bwi);
         float w = power_heuristic(bpdf, lpdf);
         // f and w are kept apart: the resolve forms sc w (f * Le) in the reference's order once
@@ -1026,7 +1070,7 @@ DEV uint32_t shade_vertex(const DevScene& S, const WaveState& W, const PathSet& 
                           uint32_t pass, float ty, uint32_t vfin, float4 hv, const Ray& ray, uint32_t pix,
                           uint32_t nid, uint32_t sid) {
   const bool spec = (vfin & VF_SPEC) != 0;
-  bool app_sh = false, app_mis = false, app_cont = false;
+  bool app_sh = false, app_mis = false, app_cont = false, mis_culled = false;
   SampleKey k = sample_key(seed, pass, pix, nid);
   DG dgg, dgs;
   float eps;
@@ -1083,8 +1127,8 @@ DEV uint32_t shade_vertex(const DevScene& S, const WaveState& W, const PathSet& 
   // the continuation ray Ray p wi eps infinity (Path.hs:79) with its kd_root flag (dev_trace.h)
   O.dir[o] = make_float4(cwi.x, cwi.y, cwi.z, kd_flag_w(pc, !cont || kd_root(S, Ray{p, cwi, eps, INFINITY})));
   direct_setup<F>(S, W, O, o, k, bsdf, wo, p, eps, 1 + 4 * depth, 1 + 3 * depth, 2 + 4 * depth, 2 + 3 * depth, vf,
-                  app_mis, app_sh, m, sid, depth);
-  O.mdir[o] = m.mdir;
+                  app_mis, app_sh, mis_culled, m, sid, depth);
+  if (app_mis) O.mdir[o] = m.mdir;                                    // read only under VF_MIS
   if constexpr (factored<F>()) O.fac[o] = m.fac;
   O.meta[o] = make_uint4(vf, pix, nid, sid);
   // what the next launches need of the vertex: cf (factored: the continuation's factors and the
@@ -1101,7 +1145,8 @@ DEV uint32_t shade_vertex(const DevScene& S, const WaveState& W, const PathSet& 
   SBW(W, SB_SHD, 16, app_sh);
   SBW(W, SB_LSC, 64, !factored<F>() && app_sh);
   SBW(W, SB_BSC, 64, !factored<F>() && app_mis);
-  return QF_RESOLVE | (app_sh ? QF_ANY : 0u) | (app_mis ? QF_MIS : 0u) | (app_cont ? QF_CONT : 0u);
+  return QF_RESOLVE | (app_sh ? QF_ANY : 0u) | (app_mis ? QF_MIS : 0u) | (app_cont ? QF_CONT : 0u) |
+         (mis_culled ? QF_MISCULL : 0u);
 }
 
 // A path whose continuation ray of depth d missed, or that reached maxDepth: Le of the escaped ray
@@ -1297,7 +1342,7 @@ static __global__ __launch_bounds__(256) SHADE_OCC void k_shade_dl(const DevScen
     const float4 hv = P.hit[i], ro = W.corg[i], rdv = P.dir[i];
     const Ray ray{mk(ro.x, ro.y, ro.z), mk(rdv.x, rdv.y, rdv.z), ro.w, INFINITY};
     const bool hit = __float_as_uint(hv.y) != REF_NONE;
-    bool app_sh = false, app_mis = false, next = false;
+    bool app_sh = false, app_mis = false, mis_culled = false, next = false;
     uint32_t mask = W.dl_mask[i], vf = 0u;
     float4 no = ro, nd = rdv;
     int nlev = 0;
@@ -1319,8 +1364,8 @@ static __global__ __launch_bounds__(256) SHADE_OCC void k_shade_dl(const DevScen
       m.fac = make_float4(0.f, 0.f, 0.f, 0.f);
       const float* lr = (factored<F>() && bsdf.n) ? bsdf.b[0].r : nullptr;
       const uint32_t rtex = lr ? (uint32_t)((const char*)lr - (const char*)gen(S.textures)) : ~0u;
-      direct_setup<F>(S, W, P, i, k, bsdf, wo, p, eps, 2 * d, 2 * d, 1 + 2 * d, 1 + 2 * d, vf, app_mis, app_sh, m, i);
-      P.mdir[i] = m.mdir;
+      direct_setup<F>(S, W, P, i, k, bsdf, wo, p, eps, 2 * d, 2 * d, 1 + 2 * d, 1 + 2 * d, vf, app_mis, app_sh, mis_culled, m, i);
+      if (app_mis) P.mdir[i] = m.mdir;
       if constexpr (factored<F>()) { P.fac[i] = m.fac; P.cf[i] = make_float4(0.f, 1.f, __uint_as_float(rtex), 0.f); }
       if (d + 1 != S.max_depth) {                                          // cont: d == md -> black
         Sp fr, ft; V3 wr, wt;
@@ -1364,7 +1409,7 @@ static __global__ __launch_bounds__(256) SHADE_OCC void k_shade_dl(const DevScen
     // k_resolve finalises on TERM; the depth bits carry the next ray's level
     P.meta[i] = make_uint4((hit ? (vf | (next ? 0u : VF_TERM)) : 0u) | vf_make(-1, nlev), meta.y, meta.z, meta.w);
     W.qflag[e] = (uint8_t)((hit ? QF_RESOLVE : 0u) | (app_sh ? QF_ANY : 0u) | (app_mis ? QF_MIS : 0u) |
-                           (next ? QF_CONT : 0u));
+                           (next ? QF_CONT : 0u) | (mis_culled ? QF_MISCULL : 0u));
   }
   flush_dropped(C, n_drop);
 }
@@ -1453,9 +1498,9 @@ static __global__ __launch_bounds__(256) void k_raygen_list(const DevScene* __re
   init_path(*Sptr, W, i, list[3 * i], list[3 * i + 1], (uint32_t)list[3 * i + 2], seed, pass);
 }
 
-// queue counters for a fresh wave of n paths: SHADE0 = CLOSEST = n, the rest 0
+// queue counters for a fresh wave of n paths: SHADE0 = CLOSEST = n, the rest (QC_MISCULL too) 0
 static __global__ void k_reset_queues(uint32_t* qcount, uint32_t n) {
-  if (threadIdx.x < Q_N) qcount[threadIdx.x] = (threadIdx.x == Q_SHADE0 || threadIdx.x == Q_CLOSEST) ? n : 0u;
+  if (threadIdx.x < QC_N) qcount[threadIdx.x] = (threadIdx.x == Q_SHADE0 || threadIdx.x == Q_CLOSEST) ? n : 0u;
 }
 // Before shade(d): the trace / resolve queues of this iteration are consumed.  Account the rays
 // they held (Q_CLOSEST = continuation (camera at d = 0) rays of d + MIS rays of d - 1; Q_ANY =
@@ -1466,8 +1511,11 @@ static __global__ void k_stage(uint32_t* qcount, int qin, int depth, Counters* C
   if (threadIdx.x != 0) return;
   unsigned long long alive = (fused && depth > 0) ? qcount[Q_RESOLVE] : qcount[qin];
   unsigned long long closest = qcount[Q_CLOSEST], any = qcount[Q_ANY];
+  // MIS queries of d - 1 that direct_setup answered (mis_cull_test): queries all the same, not queued
+  const unsigned long long culled = qcount[QC_MISCULL];
   if (depth == 0) C->cam += alive; else C->cont += alive;
-  C->mis += closest - alive;
+  C->mis += closest - alive + culled;
+  C->mis_culled += culled;
   C->shadow += any;
   C->vertices += alive;
 }
@@ -1478,27 +1526,35 @@ static __global__ void k_stage(uint32_t* qcount, int qin, int depth, Counters* C
 // three small launches instead of same-address atomics from every wave (those serialise across
 // the 8 XCDs and cost milliseconds per bounce).  Closest queue = all MIS entries, then all
 // continuation entries, each in shade-queue order (paths stay in raygen order: coherent rays).
-DEV void wave_counts(const uint8_t* __restrict__ flag, uint32_t wb, uint32_t n, uint32_t cnt[4]) {
+template <int NC>
+DEV void wave_counts(const uint8_t* __restrict__ flag, uint32_t wb, uint32_t n, uint32_t cnt[NC]) {
   const uint32_t lane = threadIdx.x & 63u;
-  cnt[0] = cnt[1] = cnt[2] = cnt[3] = 0u;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) cnt[c] = 0u;
   for (uint32_t k = 0; k < 16; ++k) {
     uint32_t e = wb + k * 64u + lane;
     uint32_t f = e < n ? flag[e] : 0u;
 #pragma unroll
-    for (int c = 0; c < 4; ++c) cnt[c] += (uint32_t)__popcll(__ballot((f >> c) & 1u));
+    for (int c = 0; c < NC; ++c) cnt[c] += (uint32_t)__popcll(__ballot((f >> c) & 1u));
   }
 }
 
-static __global__ __launch_bounds__(256) void k_compact_count(WaveState W, int qin) {
-  __shared__ uint32_t s[4][4];
+// blk: per block the four scattered counts [nb][4], the totals' row [4], then the blocks' culled
+// counts [nb] (summed by the scan, never scattered)
+static __global__ __launch_bounds__(256) void k_compact_count(WaveState W, uint32_t nb, int qin) {
+  __shared__ uint32_t s[4][QF_COUNTS];
   const uint32_t n = W.qcount[qin];
   const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
   const uint32_t wb = blockIdx.x * COMPACT_CHUNK + w * 1024u;
-  uint32_t cnt[4];
-  wave_counts(W.qflag, wb, n, cnt);
-  if (lane == 0) for (int c = 0; c < 4; ++c) s[w][c] = cnt[c];
+  uint32_t cnt[QF_COUNTS];
+  wave_counts<QF_COUNTS>(W.qflag, wb, n, cnt);
+  if (lane == 0) for (int c = 0; c < QF_COUNTS; ++c) s[w][c] = cnt[c];
   __syncthreads();
-  if (threadIdx.x < 4) W.blk[4 * blockIdx.x + threadIdx.x] = s[0][threadIdx.x] + s[1][threadIdx.x] + s[2][threadIdx.x] + s[3][threadIdx.x];
+  if (threadIdx.x < QF_COUNTS) {
+    const uint32_t v = s[0][threadIdx.x] + s[1][threadIdx.x] + s[2][threadIdx.x] + s[3][threadIdx.x];
+    if (threadIdx.x < 4) W.blk[4 * blockIdx.x + threadIdx.x] = v;
+    else W.blk[4 * nb + 4 + blockIdx.x] = v;
+  }
 }
 
 // one block of 1024: exclusive scan of the per-block counts; queue lengths for the next launches
@@ -1506,12 +1562,17 @@ static __global__ __launch_bounds__(256) void k_compact_count(WaveState W, int q
 // continuation count (k_stage); otherwise the next shade input is the continuation list.
 static __global__ __launch_bounds__(1024) void k_compact_scan(WaveState W, uint32_t nb, int qin, int fused) {
   __shared__ uint32_t s[1024][4];
+  __shared__ uint32_t culled[16];                            // per wave
   const uint32_t t = threadIdx.x;
   const uint32_t seg = (nb + 1023u) / 1024u, b0 = t * seg, b1 = min(nb, b0 + seg);
-  uint32_t sum[4] = {0u, 0u, 0u, 0u};
-  for (uint32_t b = b0; b < b1; ++b)
+  uint32_t sum[4] = {0u, 0u, 0u, 0u}, cull = 0u;
+  for (uint32_t b = b0; b < b1; ++b) {
     for (int c = 0; c < 4; ++c) sum[c] += W.blk[4 * b + c];
+    cull += W.blk[4 * nb + 4 + b];
+  }
   for (int c = 0; c < 4; ++c) s[t][c] = sum[c];
+  cull = (uint32_t)wave_sum_u64((unsigned long long)cull);   // the culled total needs no scan
+  if ((t & 63u) == 0u) culled[t >> 6] = cull;
   __syncthreads();
   for (uint32_t off = 1; off < 1024; off <<= 1) {          // Hillis-Steele inclusive scan
     uint32_t v[4];
@@ -1531,6 +1592,9 @@ static __global__ __launch_bounds__(1024) void k_compact_scan(WaveState W, uint3
     W.qcount[Q_ANY] = ta;
     W.qcount[Q_CLOSEST] = tm + tc;
     W.qcount[qin ^ 1] = fused ? tr : tc;
+    uint32_t tq = 0u;
+    for (int w = 0; w < 16; ++w) tq += culled[w];
+    W.qcount[QC_MISCULL] = tq;
   }
 }
 
@@ -1541,7 +1605,7 @@ static __global__ __launch_bounds__(256) void k_compact_scatter(WaveState W, uin
   const uint32_t wb = blockIdx.x * COMPACT_CHUNK + w * 1024u;
   if (blockIdx.x * COMPACT_CHUNK >= n) return;               // whole block past the queue
   uint32_t cnt[4];
-  wave_counts(W.qflag, wb, n, cnt);
+  wave_counts<4>(W.qflag, wb, n, cnt);
   if (lane == 0) for (int c = 0; c < 4; ++c) s[w][c] = cnt[c];
   __syncthreads();
   uint32_t off[4];

@@ -112,6 +112,16 @@ class Context:
         _check(_ffi.hip().bling_debug_scene_info(self._h, buf, len(buf), None))
         return json.loads(buf.value.decode())
 
+    def mis_culled(self) -> int:
+        """bling_debug_mis_culled: the last pass's BSDF-MIS queries that were answered without a walk."""
+        n = C.c_uint64()
+        _check(_ffi.hip().bling_debug_mis_culled(self._h, C.byref(n)))
+        return int(n.value)
+
+    def set_mis_cull(self, on: bool):
+        """bling_debug_set_mis_cull: switch the MIS cull for every later call (sample_li included)."""
+        _check(_ffi.hip().bling_debug_set_mis_cull(self._h, 1 if on else 0))
+
     def stream_bytes(self) -> dict:
         """bling_debug_stream_bytes: k_shade's path-state bytes of the last pass per stream,
         {name: (read, written)} (BLING_STREAM_STATS builds only)."""

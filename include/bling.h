@@ -64,6 +64,12 @@ typedef struct bling_pass_params {
 #define BLING_PASS_TILE_IMAGES     4u
 /* bling_render only: RegionStarted / SamplesAdded reports per sample window before each PassDone */
 #define BLING_PASS_REGION_EVENTS   8u
+/* Walk every BSDF-MIS ray.  By default a vertex whose sampled light is an area light answers its MIS
+ * query itself when the light's own shape rejects the ray (its candidate is then exactly zero,
+ * DESIGN.md section 3): same film, same counts, a shorter closest-hit queue.  The switch is for A/B
+ * measurements and the tests.  BLING_DEBUG_VERTEX builds never cull (they record every vertex's MIS
+ * hit distance, record 29), with or without this bit. */
+#define BLING_PASS_NO_MIS_CULL     16u
 
 typedef struct bling_stats {
     uint64_t camera_samples;   /* paths started                                               */
@@ -307,6 +313,15 @@ int bling_debug_light_records(bling_ctx* ctx, uint32_t seed, uint32_t pass_index
 #define BLING_STREAM_NAMES "queue,hit,meta,org,dir,mdir,mhit,occ,fac,cf,T,L,Tn,lsc,bsc,sh_o,sh_d,result,qflag"
 #define BLING_N_STREAMS 19
 int bling_debug_stream_bytes(bling_ctx* ctx, uint64_t* out, size_t n, size_t* n_streams);
+
+/* Diagnostics (no reference counterpart): of the rays_mis of the context's last bling_render_pass*,
+ * the queries the shading kernels answered themselves (the MIS cull, BLING_PASS_NO_MIS_CULL); the
+ * closest-hit kernel walked rays_camera + rays_continuation + rays_mis - *out queries. */
+int bling_debug_mis_culled(bling_ctx* ctx, uint64_t* out);
+/* on = 0: every later call on the context (bling_sample_li, which takes no pass flags, included)
+ * walks all its MIS rays, as BLING_PASS_NO_MIS_CULL does for one pass; on = 1 (the default) restores
+ * the cull.  Per-sample radiance is summed by no atomics, so it can be compared bit for bit. */
+int bling_debug_set_mis_cull(bling_ctx* ctx, int on);
 
 /* The uploaded scene's acceleration / kernel plan as one JSON object (BVH2 and BVH4 depth and
  * sizes, the BVH4 stack bound, the LDS plans, the packet walk, the in-line shadow test), written
