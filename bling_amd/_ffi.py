@@ -139,7 +139,7 @@ class Progress(C.Structure):
 
 PROGRESS_STARTED, PROGRESS_SAMPLES_ADDED, PROGRESS_REGION_STARTED, PROGRESS_PASS_DONE = 0, 1, 2, 3
 ProgressFn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(Progress))
-STREAM_NAMES = "queue,hit,meta,org,dir,mdir,mhit,occ,fac,cf,T,L,Tn,lsc,bsc,sh_o,sh_d,result,qflag".split(",")
+STREAM_NAMES = "queue,hit,meta,org,dir,mdir,mhit,fm,occ,fac,rtex,T,L,Tn,lsc,bsc,sh_o,sh_d,result,qflag".split(",")
 
 
 def hip() -> C.CDLL:

@@ -56,10 +56,10 @@ struct DBuf {
 
 
 // device bytes per path in flight, for sizing waves: per path set the SoA streams of wavefront.h
-// PathSet (org, dir, hit, meta, mdir, fac, cf, sh_o, sh_d: 16 B each; mhit 8 B; occ 4 B), T and L
-// (64 B each) and, for the non-factored profiles, Tn, lsc and bsc (64 B each); two sets for the Path
+// PathSet (org, dir, hit, meta, mdir, fac, sh_o, sh_d: 16 B each; mhit 8 B; fm, occ, rtex 4 B each),
+// T and L (64 B each) and, for the non-factored profiles, Tn, lsc and bsc (64 B each); two sets for the Path
 // pipeline, plus result, img, six queue words and the queue flag
-constexpr uint64_t kSetBytes = 9 * 16 + 8 + 4 + 64 + 64;
+constexpr uint64_t kSetBytes = 8 * 16 + 8 + 3 * 4 + 64 + 64;
 constexpr uint64_t kSetSpectraBytes = 3 * 64;
 constexpr uint64_t kPathFixedBytes = 16 + 8 + 6 * 4 + 1 + 4 + 2 * 4;   // ... + the k_march results (2 words)
 // DirectLighting adds the continuation origin, the sibling mask and one parked ray (org, dir,
@@ -130,23 +130,24 @@ struct bling_ctx {
   // path state (WaveState): two sets of per-slot records (PathSet), by-sample arrays, queues
   uint32_t cap = 0;
   struct SetBufs {
-    DBuf<float4> org, dir, hit, mdir, fac, cf, sh_o, sh_d, T, Tn, L, lsc, bsc;
+    DBuf<float4> org, dir, hit, mdir, fac, sh_o, sh_d, T, Tn, L, lsc, bsc;
     DBuf<uint4> meta;
     DBuf<float2> mhit;
-    DBuf<uint32_t> occ;
+    DBuf<float> fm;
+    DBuf<uint32_t> occ, rtex;
     void alloc(uint32_t n, bool spectra) {
-      for (auto* b : {&org, &dir, &hit, &mdir, &fac, &cf, &sh_o, &sh_d}) b->alloc(n);
-      meta.alloc(n); mhit.alloc(n); occ.alloc(n);
+      for (auto* b : {&org, &dir, &hit, &mdir, &fac, &sh_o, &sh_d}) b->alloc(n);
+      meta.alloc(n); mhit.alloc(n); fm.alloc(n); occ.alloc(n); rtex.alloc(n);
       T.alloc((size_t)4 * n); L.alloc((size_t)4 * n);
       if (spectra) { Tn.alloc((size_t)4 * n); lsc.alloc((size_t)4 * n); bsc.alloc((size_t)4 * n); }
       else { Tn.free(); lsc.free(); bsc.free(); }
     }
     void free() {
-      for (auto* b : {&org, &dir, &hit, &mdir, &fac, &cf, &sh_o, &sh_d, &T, &Tn, &L, &lsc, &bsc}) b->free();
-      meta.free(); mhit.free(); occ.free();
+      for (auto* b : {&org, &dir, &hit, &mdir, &fac, &sh_o, &sh_d, &T, &Tn, &L, &lsc, &bsc}) b->free();
+      meta.free(); mhit.free(); fm.free(); occ.free(); rtex.free();
     }
     PathSet view() const {
-      return PathSet{org.p, dir.p, hit.p, meta.p, mdir.p, mhit.p, occ.p, fac.p, cf.p, sh_o.p, sh_d.p,
+      return PathSet{org.p, dir.p, hit.p, meta.p, mdir.p, mhit.p, fm.p, occ.p, fac.p, rtex.p, sh_o.p, sh_d.p,
                      T.p, Tn.p, L.p, lsc.p, bsc.p};
     }
   } set[2];

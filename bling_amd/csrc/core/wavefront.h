@@ -92,9 +92,11 @@ enum QueueId : int { Q_SHADE0 = 0, Q_SHADE1 = 1, Q_CLOSEST = 2, Q_ANY = 3, Q_RES
 //   mdir  wi.xyz, w       BSDF-MIS ray direction and its MIS weight
 //   mhit  t, ref          BSDF-MIS ray's closest hit (k_trace_closest)
 //   occ   0 / 1           the shadow ray is occluded (k_trace_any)
-//   fac   s1 f_mis, s1, s2, w / pdf    factored candidates (factored profiles)
-//   cf    s1, pc, rtex, - factored profiles: the continuation's f = r s1, the RR pc and the lobe
-//                         spectrum's byte offset, so the next launch forms T' = (f T) / pc itself
+//   fm    s1 of the BSDF-MIS candidate (factored profiles; written and read only with a MIS ray)
+//   fac   s1c, s1, s2, w / pdf    factored profiles: the continuation's f = r s1c and the light
+//                         sample's candidate scalars, so the next launch forms T' = (f T) / pc itself
+//                         (pc = |dir.w|) and expands the candidate
+//   rtex  factored profiles: the lobe spectrum's byte offset (~0u = white)
 //   sh_o, sh_d            the light sample's shadow ray (o, tmin | d, tmax)
 //   T (throughput of the vertex), Tn (after the continuation; non-factored profiles), L (radiance so
 //   far), lsc / bsc (light- / BSDF-sample candidates; non-factored profiles): 16-band spectra, one
@@ -104,34 +106,50 @@ struct PathSet {
   uint4* meta;
   float4* mdir;
   float2* mhit;
+  float* fm;
   uint32_t* occ;
-  float4 *fac, *cf, *sh_o, *sh_d;
+  float4* fac;
+  uint32_t* rtex;
+  float4 *sh_o, *sh_d;
   float4 *T, *Tn, *L, *lsc, *bsc;
 };
 
 // a vertex's estimate as its shade launch writes it and the next launch's resolve reads it
-struct Est { float4 mdir, fac, cf; float2 mhit; uint32_t occ; };
+struct Est { float4 mdir, fac; float2 mhit; uint32_t occ; float fm; uint32_t rtex; };
 DEV Est load_est(const PathSet& P, uint32_t s, uint32_t vf, bool factored_) {
   Est m;
   m.mdir = P.mdir[s];
   m.mhit = (vf & 2u) ? P.mhit[s] : make_float2(0.f, 0.f);
   m.occ = (vf & 1u) ? P.occ[s] : 0u;
   m.fac = factored_ ? P.fac[s] : make_float4(0.f, 0.f, 0.f, 0.f);
-  m.cf = factored_ ? P.cf[s] : make_float4(0.f, 0.f, 0.f, 0.f);
+  m.fm = (factored_ && (vf & 2u)) ? P.fm[s] : 0.f;
+  m.rtex = factored_ ? P.rtex[s] : ~0u;
   return m;
 }
-// The same record loaded without waiting for the metadata: the traced outcomes (mhit, occ) are read
-// whatever the flags say (their slots always exist; a value whose ray was not traced is never used),
-// so every load of the record issues together with the metadata's instead of one memory latency
-// after it.  The flags still select what the resolve uses.
-DEV Est load_est_eager(const PathSet& P, uint32_t s, bool factored_) {
-  Est m;
-  m.mdir = P.mdir[s];
-  m.mhit = P.mhit[s];
+// The same record for the fused resolve, in two parts.  load_est_fused: occ and the factored scalars,
+// read whatever the flags say (their slots always exist; a value whose ray was not traced is never
+// used), so they issue with the metadata's loads.  load_est_mis: the BSDF-MIS ray's records (mdir,
+// mhit: 24 B, and the factored fm).  Eager (lazy = false), they too are read whatever the flags say:
+// where nearly every vertex has such a ray, round 5 measured flag-predicated loads at -0.6 %.  Where
+// the MIS cull answers nearly every query (0.65 % of C2's vertices keep a MIS ray) only the lanes
+// with VF_MIS load them.  k_shade calls it after it has issued every other load of the entry (occ,
+// fac, rtex, T): the compiler sinks the first use of mdir (|w|) into the predicated block and
+// waits there, so whatever is issued after that block starts one memory latency late.
+// mis_lazy<F>(): the profile the lazy form was measured on (cornell, C2: every light an area light,
+// so mis_cull_test applies to every vertex).  k_shade takes the lazy form only while the cull is on
+// (WaveState::mis_cull); the other profiles keep the eager loads.
+template <uint32_t F>
+constexpr bool mis_lazy() { return (F & ~(FT_MATTE | FT_AREA | FT_TRIS)) == 0; }
+DEV void load_est_fused(Est& m, const PathSet& P, uint32_t s, bool factored_) {
   m.occ = P.occ[s];
   m.fac = factored_ ? P.fac[s] : make_float4(0.f, 0.f, 0.f, 0.f);
-  m.cf = factored_ ? P.cf[s] : make_float4(0.f, 0.f, 0.f, 0.f);
-  return m;
+  m.rtex = factored_ ? P.rtex[s] : ~0u;
+}
+DEV void load_est_mis(Est& m, const PathSet& P, uint32_t s, uint32_t vf, bool factored_, bool lazy) {
+  const bool mis = !lazy || (vf & VF_MIS) != 0u;
+  m.mdir = mis ? P.mdir[s] : make_float4(0.f, 0.f, 0.f, 0.f);
+  m.mhit = mis ? P.mhit[s] : make_float2(0.f, 0.f);
+  m.fm = (factored_ && (vf & VF_MIS) != 0u) ? P.fm[s] : 0.f;
 }
 
 struct WaveState {
@@ -199,7 +217,7 @@ struct Counters {
 #ifndef BLING_STREAM_STATS
 #define BLING_STREAM_STATS 0
 #endif
-enum StreamId : int { SB_QUEUE, SB_HIT, SB_META, SB_ORG, SB_DIR, SB_MDIR, SB_MHIT, SB_OCC, SB_FAC, SB_CF, SB_T, SB_L,
+enum StreamId : int { SB_QUEUE, SB_HIT, SB_META, SB_ORG, SB_DIR, SB_MDIR, SB_MHIT, SB_FM, SB_OCC, SB_FAC, SB_RTEX, SB_T, SB_L,
                       SB_TN, SB_LSC, SB_BSC, SB_SHO, SB_SHD, SB_RESULT, SB_QFLAG };
 static_assert(SB_QFLAG + 1 == BLING_N_STREAMS, "stream list of include/bling.h");
 DEV void sb_count(unsigned long long* sb, int k, bool wr, uint32_t bytes, bool pred) {
@@ -785,8 +803,8 @@ static __global__ __launch_bounds__(256) void k_trace_any_bf(const DevScene* __r
 // radiance), the two candidate spectra of a vertex are
 //   light sample:  lsc = ((0 + (r * s1) * s2) * Le) * (w / pdf)     (evalBsdf, sampleLightMis)
 //   BSDF sample:   bsc = r * s1                                      (sampleBsdf, sampleBsdfMis)
-// and the continuation's throughput is (r * s1 * T) / pc, so k_shade stores scalars (fac, cf) and the
-// texture offset (cf.z) instead of three 64-B spectra, and the next launch expands them
+// and the continuation's throughput is (r * s1 * T) / pc, so k_shade stores scalars (fac, fm) and the
+// texture offset (rtex) instead of three 64-B spectra, and the next launch expands them
 // with the same operations in the same order: bit-identical candidates and throughputs.
 template <uint32_t F>
 constexpr bool factored() { return (F & ~(FT_MATTE | FT_AREA | FT_TRIS)) == 0; }
@@ -881,7 +899,8 @@ DEV void direct_setup(const DevScene& S, const WaveState& W, const PathSet& O, u
           app_sh = true;
         }
       }
-      m.fac = make_float4(fm, fs1, fs2, wpdf);
+      m.fm = fm;                                                     // m.fac.x: the caller's s1c
+      m.fac.y = fs1; m.fac.z = fs2; m.fac.w = wpdf;
       return;
     }
     // BSDF half of estimateDirect: sampleBsdfMis (Scene.hs:71-82)
@@ -995,7 +1014,7 @@ DEV Sp resolve_L(const DevScene& S, const WaveState& W, uint32_t s, uint32_t vf,
     if constexpr (factored<F>()) {
       if (vf & (VF_SH | VF_MIS)) {
         fc = m.fac;
-        rf = lobe_r(S, __float_as_uint(m.cf.z));
+        rf = lobe_r(S, m.rtex);
       }
       if ((vf & VF_SH) && m.occ == 0u)
         ls = sscale(diffuse1_e(rf, fc.y, fc.z) * sload(light_rec<F>(S, ln).radiance), fc.w);
@@ -1011,7 +1030,7 @@ DEV Sp resolve_L(const DevScene& S, const WaveState& W, uint32_t s, uint32_t vf,
       V3 wi = mk(d.x, d.y, d.z);
       DVREC(W, sid, dvd, 29, ref == REF_NONE ? INFINITY : m.mhit.x);
       if (ref == REF_NONE) {
-        const Sp bf = factored<F>() ? diffuse1_f(rf, fc.x) : load_sp(W.cur.bsc, s);
+        const Sp bf = factored<F>() ? diffuse1_f(rf, m.fm) : load_sp(W.cur.bsc, s);
         SBR(W, SB_BSC, 64, !factored<F>());
         bs = sscale(bf * light_le<F>(Lt, wi), fabsf(d.w));           // le l ray (w: the kd_root flag's sign)
       } else if ((ref >> 30) == REF_SHAPE) {
@@ -1020,7 +1039,7 @@ DEV Sp resolve_L(const DevScene& S, const WaveState& W, uint32_t s, uint32_t vf,
         if (hs.light == ln) {                                         // l' == l (Light.hs:48-50)
           DG dg = shape_dg<F>(hs, Ray{mk(o.x, o.y, o.z), wi, o.w, INFINITY}, m.mhit.x);
           Sp le = dot(dg.n, -wi) > 0.f ? sload(gen(S.lights[ln]).radiance) : sconst(0.f);   // intLe (-wi): trap T6
-          const Sp bf = factored<F>() ? diffuse1_f(rf, fc.x) : load_sp(W.cur.bsc, s);
+          const Sp bf = factored<F>() ? diffuse1_f(rf, m.fm) : load_sp(W.cur.bsc, s);
           bs = sscale(bf * le, fabsf(d.w));
         }
       }
@@ -1044,18 +1063,17 @@ DEV Sp resolve_L(const DevScene& S, const WaveState& W, uint32_t s, uint32_t vf,
 
 // The throughput of the vertex a continuation ray of slot s leads to, from the throughput Tv of the
 // vertex that sampled it (Path.hs:82: t' = f t / pc).  The shading launch stores f and pc, not t':
-// factored profiles the factors of f = r s1 (cf.x, texture offset cf.z) and pc in cf.y; the others
-// the spectrum f (Tn) and pc in the continuation direction's w.  The next launch, which holds Tv
+// factored profiles the factors of f = r s1 (fac.x, the texture offset rtex); the others the spectrum
+// f (Tn); both pc in the continuation direction's w (kd_flag_w).  The next launch, which holds Tv
 // anyway, forms t' with the same operations, so the shading phase needs only sY(T) (the RR bound)
 // instead of the 16-band throughput.
 template <uint32_t F>
-DEV Sp next_throughput(const DevScene& S, const PathSet& P, uint32_t s, const float4 cf, const Sp& Tv, float pc) {
+DEV Sp next_throughput(const DevScene& S, const PathSet& P, uint32_t s, const Est& m, const Sp& Tv, float pc) {
   if constexpr (factored<F>()) {
-    (void)pc;
-    const Sp f = diffuse1_f(lobe_r(S, __float_as_uint(cf.z)), cf.x);
-    return sscale(f * Tv, 1.f / cf.y);
+    const Sp f = diffuse1_f(lobe_r(S, m.rtex), m.fac.x);
+    return sscale(f * Tv, 1.f / pc);
   } else {
-    (void)cf;
+    (void)m;
     return sscale(load_sp(P.Tn, s) * Tv, 1.f / pc);
   }
 }
@@ -1088,6 +1106,7 @@ DEV uint32_t shade_vertex(const DevScene& S, const WaveState& W, const PathSet& 
   Est m;
   m.mdir = make_float4(0.f, 0.f, 0.f, 0.f);
   m.fac = make_float4(0.f, 0.f, 0.f, 0.f);
+  m.fm = 0.f;
   const float* r = (factored<F>() && bsdf.n) ? bsdf.b[0].r : nullptr;
   const uint32_t rtex = r ? (uint32_t)((const char*)r - (const char*)gen(S.textures)) : ~0u;
   // Russian roulette + continuation (Path.hs:68-87)
@@ -1120,26 +1139,31 @@ DEV uint32_t shade_vertex(const DevScene& S, const WaveState& W, const PathSet& 
     }
   }
   if (!cont) vf |= VF_TERM;
-  // the continuation is written before the one-light estimate is set up, so none of its state is
-  // live across that (the sample dimensions are independent draws: the order changes no value)
-  if constexpr (factored<F>()) O.cf[o] = make_float4(s1c, pc, __uint_as_float(rtex), 0.f);
+  // the continuation is written before the one-light estimate is set up, so of its state only s1c
+  // (factored profiles: fac.x) is live across that (the sample dimensions are independent draws: the
+  // order changes no value)
+  if constexpr (factored<F>()) { O.rtex[o] = rtex; m.fac.x = s1c; }
   O.org[o] = make_float4(p.x, p.y, p.z, eps);
   // the continuation ray Ray p wi eps infinity (Path.hs:79) with its kd_root flag (dev_trace.h)
   O.dir[o] = make_float4(cwi.x, cwi.y, cwi.z, kd_flag_w(pc, !cont || kd_root(S, Ray{p, cwi, eps, INFINITY})));
   direct_setup<F>(S, W, O, o, k, bsdf, wo, p, eps, 1 + 4 * depth, 1 + 3 * depth, 2 + 4 * depth, 2 + 3 * depth, vf,
                   app_mis, app_sh, mis_culled, m, sid, depth);
-  if (app_mis) O.mdir[o] = m.mdir;                                    // read only under VF_MIS
+  if (app_mis) {                                                      // read only under VF_MIS
+    O.mdir[o] = m.mdir;
+    if constexpr (factored<F>()) O.fm[o] = m.fm;
+  }
   if constexpr (factored<F>()) O.fac[o] = m.fac;
   O.meta[o] = make_uint4(vf, pix, nid, sid);
-  // what the next launches need of the vertex: cf (factored: the continuation's factors and the
-  // lobe offset the candidates use), the origin of the continuation / MIS rays, the continuation
-  // direction and pc, the MIS direction and weight, the candidates' scalars, the metadata; the
-  // shadow ray and, in the spectral profiles, the candidate spectra
-  SBW(W, SB_CF, 16, factored<F>() && (app_cont || app_sh || app_mis));
+  // what the next launches need of the vertex: fac and rtex (factored: the continuation's factor,
+  // the light candidate's scalars and the lobe offset both use), the origin of the continuation /
+  // MIS rays, the continuation direction and pc, the MIS direction, weight and (factored) factor,
+  // the metadata; the shadow ray and, in the spectral profiles, the candidate spectra
+  SBW(W, SB_FAC, 16, factored<F>() && (app_cont || app_sh || app_mis));
+  SBW(W, SB_RTEX, 4, factored<F>() && (app_cont || app_sh || app_mis));
   SBW(W, SB_ORG, 16, app_cont || app_mis);
   SBW(W, SB_DIR, 16, app_cont);
   SBW(W, SB_MDIR, 16, app_mis);
-  SBW(W, SB_FAC, 16, factored<F>() && (app_sh || app_mis));
+  SBW(W, SB_FM, 4, factored<F>() && app_mis);
   SBW(W, SB_META, 16, true);
   SBW(W, SB_SHO, 16, app_sh);
   SBW(W, SB_SHD, 16, app_sh);
@@ -1228,8 +1252,9 @@ static __global__ __launch_bounds__(256) SHADE_OCC void k_shade(const DevScene* 
       uint4 meta = make_uint4(0u, 0u, 0u, 0u);
       if (e < n) {
         s = qcur;
-        // every record of the slot is loaded at once (no load waits on another's value): hit,
-        // metadata, the ray of the vertex (the ring hands it to the shading lane) and the estimate
+        // the records of the slot are loaded at once (no load waits on another's value): hit,
+        // metadata, the ray of the vertex (the ring hands it to the shading lane) and, below, the
+        // estimate, T and L; only the lazy form of the MIS ray's records waits for the metadata
         hv = W.cur.hit[s];
         meta = W.cur.meta[s];
         ro = W.cur.org[s];
@@ -1250,16 +1275,18 @@ static __global__ __launch_bounds__(256) SHADE_OCC void k_shade(const DevScene* 
         Sp L = sconst(0.f);
         bool ends = false;
         Est m;
-        m.cf = make_float4(0.f, 0.f, 0.f, 0.f);
+        m.fac = make_float4(0.f, 0.f, 0.f, 0.f);
+        m.rtex = ~0u;
         Sp Tp = sconst(1.f);                                                  // T(d - 1)
         if constexpr (FUSED) {
-          m = load_est_eager(W.cur, s, factored<F>());
+          load_est_fused(m, W.cur, s, factored<F>());
           if (depth > 1) Tp = load_sp(W.cur.T, s);
+          load_est_mis(m, W.cur, s, meta.x, factored<F>(), mis_lazy<F>() && W.mis_cull != 0u);
           L = resolve_L<F>(S, W, s, meta.x, m, Tp, depth == 1, meta.w, depth - 1, ro);
           SBR(W, SB_MDIR, 16, (meta.x & VF_MIS) != 0u);
           SBR(W, SB_MHIT, 8, (meta.x & VF_MIS) != 0u);
           SBR(W, SB_OCC, 4, (meta.x & VF_SH) != 0u);
-          SBR(W, SB_FAC, 16, factored<F>() && (meta.x & (VF_SH | VF_MIS)) != 0u);
+          SBR(W, SB_FM, 4, factored<F>() && (meta.x & VF_MIS) != 0u);
           SBR(W, SB_T, 64, depth > 1);
           SBR(W, SB_L, 64, depth > 1);
           if (meta.x & VF_TERM) { finalize(W, meta.w, L, n_drop); ends = true; }   // the path stopped at d - 1
@@ -1270,9 +1297,8 @@ static __global__ __launch_bounds__(256) SHADE_OCC void k_shade(const DevScene* 
           const bool hit = ref != REF_NONE && depth != S.max_depth;          // == vert here
           // T(d): 1 for the camera path (depth 0), else formed from T(d - 1) and the stored f, pc
           Sp Td = sconst(1.f);
-          if (FUSED && (hit || spec_miss)) Td = next_throughput<F>(S, W.cur, s, m.cf, Tp, fabsf(rdv.w));
+          if (FUSED && (hit || spec_miss)) Td = next_throughput<F>(S, W.cur, s, m, Tp, fabsf(rdv.w));
           SBR(W, SB_TN, 64, FUSED && !factored<F>() && (hit || spec_miss));
-          SBR(W, SB_CF, 16, FUSED && factored<F>() && ((hit || spec_miss) || (meta.x & (VF_SH | VF_MIS)) != 0u));
           // the vertex's ray: shading needs org and dir, a specular miss dir, T' of a spectral
           // profile dir.w (pc); the resolve needs org for a BSDF-MIS ray that hit the sampled light
           SBR(W, SB_DIR, 16, hit || spec_miss);
@@ -1289,6 +1315,15 @@ static __global__ __launch_bounds__(256) SHADE_OCC void k_shade(const DevScene* 
           } else {
             shade_end<F>(S, W, meta.w, Td, spec_miss, mk(rdv.x, rdv.y, rdv.z), L, n_drop);
           }
+        }
+        {
+          // fac / rtex: the resolve's candidates, or T(d) of a path that goes on (or escapes after a
+          // specular bounce)
+          const uint32_t ref = __float_as_uint(hv.y);
+          const bool goes_on = !ends && ((ref != REF_NONE && depth != S.max_depth) || (ref == REF_NONE && (meta.x & VF_SPEC) != 0));
+          const bool need = FUSED && factored<F>() && (goes_on || (meta.x & (VF_SH | VF_MIS)) != 0u);
+          SBR(W, SB_FAC, 16, need);
+          SBR(W, SB_RTEX, 4, need);
         }
         SBR(W, SB_QUEUE, 4, true);
         SBR(W, SB_HIT, 16, true);
@@ -1362,11 +1397,15 @@ static __global__ __launch_bounds__(256) SHADE_OCC void k_shade_dl(const DevScen
       Est m;
       m.mdir = make_float4(0.f, 0.f, 0.f, 0.f);
       m.fac = make_float4(0.f, 0.f, 0.f, 0.f);
+      m.fm = 0.f;
       const float* lr = (factored<F>() && bsdf.n) ? bsdf.b[0].r : nullptr;
       const uint32_t rtex = lr ? (uint32_t)((const char*)lr - (const char*)gen(S.textures)) : ~0u;
       direct_setup<F>(S, W, P, i, k, bsdf, wo, p, eps, 2 * d, 2 * d, 1 + 2 * d, 1 + 2 * d, vf, app_mis, app_sh, mis_culled, m, i);
-      if (app_mis) P.mdir[i] = m.mdir;
-      if constexpr (factored<F>()) { P.fac[i] = m.fac; P.cf[i] = make_float4(0.f, 1.f, __uint_as_float(rtex), 0.f); }
+      if (app_mis) {
+        P.mdir[i] = m.mdir;
+        if constexpr (factored<F>()) P.fm[i] = m.fm;
+      }
+      if constexpr (factored<F>()) { P.fac[i] = m.fac; P.rtex[i] = rtex; }   // fac.x = 0: no continuation factor
       if (d + 1 != S.max_depth) {                                          // cont: d == md -> black
         Sp fr, ft; V3 wr, wt;
         const bool hr = !(sample_bsdf_spec<F>(bsdf, wo, F_REFL, fr, wr) == 0.f);

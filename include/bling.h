@@ -310,8 +310,8 @@ int bling_debug_light_records(bling_ctx* ctx, uint32_t seed, uint32_t pass_index
  * them (a record the path uses), for the roofline's algorithmic bytes (DESIGN.md "Roofline").
  * Counted only by a BLING_STREAM_STATS build (make variant V=streams DEFS=-DBLING_STREAM_STATS=1);
  * other builds return BLING_EUNSUPPORTED.  *n_streams receives the stream count; out may be NULL. */
-#define BLING_STREAM_NAMES "queue,hit,meta,org,dir,mdir,mhit,occ,fac,cf,T,L,Tn,lsc,bsc,sh_o,sh_d,result,qflag"
-#define BLING_N_STREAMS 19
+#define BLING_STREAM_NAMES "queue,hit,meta,org,dir,mdir,mhit,fm,occ,fac,rtex,T,L,Tn,lsc,bsc,sh_o,sh_d,result,qflag"
+#define BLING_N_STREAMS 20
 int bling_debug_stream_bytes(bling_ctx* ctx, uint64_t* out, size_t n, size_t* n_streams);
 
 /* Diagnostics (no reference counterpart): of the rays_mis of the context's last bling_render_pass*,
