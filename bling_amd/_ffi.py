@@ -23,6 +23,7 @@ PASS_KERNEL_TIMING = 2     # BLING_PASS_KERNEL_TIMING
 PASS_TILE_IMAGES = 4       # BLING_PASS_TILE_IMAGES
 PASS_REGION_EVENTS = 8     # BLING_PASS_REGION_EVENTS (bling_render only)
 PASS_NO_MIS_CULL = 16      # BLING_PASS_NO_MIS_CULL
+PASS_NO_PIPELINE = 32      # BLING_PASS_NO_PIPELINE
 
 
 class PassParams(C.Structure):
@@ -126,7 +127,7 @@ def host() -> C.CDLL:
 HIP_SYMBOLS = ["bling_create", "bling_scene_upload", "bling_scene_validate", "bling_render_pass", "bling_render_pass_device",
                "bling_trace", "bling_trace_device", "bling_sample_li", "bling_sample_li_vertices", "bling_pass_tile_layout",
                "bling_film_add_tiles", "bling_film_add_shards", "bling_sppm_pass", "bling_sppm_pixel_stats", "bling_sppm_reset",
-               "bling_render", "bling_debug_stream_bytes", "bling_debug_scene_info", "bling_debug_mis_culled", "bling_debug_set_mis_cull", "bling_debug_sppm_hitpoints", "bling_debug_sppm_buckets",
+               "bling_render", "bling_debug_stream_bytes", "bling_debug_scene_info", "bling_debug_mis_culled", "bling_debug_set_mis_cull", "bling_debug_set_pipeline", "bling_debug_pass_results", "bling_debug_compact", "bling_debug_sppm_hitpoints", "bling_debug_sppm_buckets",
                "bling_light_pass", "bling_debug_light_records", "bling_destroy", "bling_last_error", "bling_version"]
 
 
@@ -203,6 +204,15 @@ def hip() -> C.CDLL:
             lib.bling_debug_mis_culled.restype = C.c_int
             lib.bling_debug_set_mis_cull.argtypes = [C.c_void_p, C.c_int]
             lib.bling_debug_set_mis_cull.restype = C.c_int
+        if hasattr(lib, "bling_debug_set_pipeline"):  # older experiment builds lack them
+            lib.bling_debug_set_pipeline.argtypes = [C.c_void_p, C.c_int]
+            lib.bling_debug_set_pipeline.restype = C.c_int
+            lib.bling_debug_pass_results.argtypes = [C.c_void_p, c_f32p, C.c_size_t, C.POINTER(C.c_size_t),
+                                                     C.POINTER(C.c_int)]
+            lib.bling_debug_pass_results.restype = C.c_int
+            lib.bling_debug_compact.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), c_u32p, C.c_size_t, C.c_size_t, C.c_int,
+                                                c_u32p, c_u32p]
+            lib.bling_debug_compact.restype = C.c_int
         if hasattr(lib, "bling_debug_stream_bytes"):
             lib.bling_debug_stream_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t,
                                                      C.POINTER(C.c_size_t)]

@@ -484,6 +484,28 @@ void upload_scene(bling_ctx* c, const bling_scene_desc* d) {
   c->light.free_all();
 }
 
+// A pass whose paths fit one wave runs as two half-waves on two streams (core_wave.h run_wave_pair_t)
+// where that measured faster: the cornell profile; BLING_PASS_NO_PIPELINE and
+// bling_debug_set_pipeline override.  Legal for the Path integrator of a product build, and only
+// while the traversal keeps its stack in LDS: the BVH4 overflow rows are indexed by a grid's thread
+// id, so two traversal launches in flight would share them.
+bool pipeline_wanted(const bling_ctx* c, const bling_pass_params* p) {
+  if (BLING_DEBUG_VERTEX || BLING_STREAM_STATS) return false;
+  if (p->flags & BLING_PASS_NO_PIPELINE) return false;
+  if (c->S.integrator == BLING_INTEGRATOR_DIRECT) return false;
+  if (c->S.stack4_need > c->S.stack4_lds) return false;
+  if (c->pipeline_mode >= 0) return c->pipeline_mode != 0;
+  return profile_of(c->features) == kProfiles[0];
+}
+
+int run_wave_pair(bling_ctx* c, const HalfWave* h, uint32_t seed, uint32_t pass, bool stats, WaveTiming* tm) {
+  int launches = 0;
+  with_profile(c->features, [&](auto prof) {
+    launches = run_wave_pair_prof<decltype(prof)::value>(c, h, seed, pass, stats, tm);
+  });
+  return launches;
+}
+
 int run_wave(bling_ctx* c, const WaveState& W, uint32_t n, uint32_t seed, uint32_t pass, bool stats,
              WaveTiming* tm = nullptr) {
   int launches = 0;
@@ -524,18 +546,19 @@ std::vector<TileDesc> pass_tiles(const DevScene& S, int rank, int world, int str
 
 // Film splat of a chunk's tiles: the register-window kernel for the filter widths the configs use,
 // the per-sample LDS-atomic kernel otherwise.  timg != NULL: the chunk's tile images into their slots.
-void launch_film(bling_ctx* c, const WaveState& P, unsigned n_tiles, float* film_dev, float* timg) {
+// td: the chunk's tile table on the device (n_tiles entries).
+void launch_film(bling_ctx* c, const WaveState& P, const TileDesc* td, unsigned n_tiles, float* film_dev, float* timg) {
   const float fw = c->S.filter_w, fh = c->S.filter_h;
   const int kx = 2 * (int)std::floor(0.5f + fw) + 1, ky = 2 * (int)std::floor(0.5f + fh) + 1;
   int sw, sh;
   tile_slot(c->S, &sw, &sh);
   hipStream_t s = c->stream;
   if (kx == 5 && ky == 5)
-    k_film_gather<5><<<n_tiles, 256 * film_split<5>(), 0, s>>>(c->dscene.p, P, c->tiles_dev.p, film_dev, timg, sw, sh);
+    k_film_gather<5><<<n_tiles, 256 * film_split<5>(), 0, s>>>(c->dscene.p, P, td, film_dev, timg, sw, sh);
   else if (kx == 7 && ky == 7)
-    k_film_gather<7><<<n_tiles, 256 * film_split<7>(), 0, s>>>(c->dscene.p, P, c->tiles_dev.p, film_dev, timg, sw, sh);
+    k_film_gather<7><<<n_tiles, 256 * film_split<7>(), 0, s>>>(c->dscene.p, P, td, film_dev, timg, sw, sh);
   else
-    k_film<<<n_tiles, 256, 0, s>>>(c->dscene.p, P, c->tiles_dev.p, film_dev, timg, sw, sh);
+    k_film<<<n_tiles, 256, 0, s>>>(c->dscene.p, P, td, film_dev, timg, sw, sh);
 }
 
 int render(bling_ctx* c, const bling_pass_params* p, float* film_dev, bling_stats* st) {
@@ -578,10 +601,14 @@ int render(bling_ctx* c, const bling_pass_params* p, float* film_dev, bling_stat
   }
   want = std::min<uint64_t>(want, (uint64_t)1 << 31);
   uint32_t chunk = (uint32_t)std::max<uint64_t>(want, 256u * spp);
-  c->ensure_paths((uint32_t)std::min<uint64_t>(chunk, std::max<uint64_t>(total, 1)));
+  // one wave, at least two tiles: two half-waves cut at a tile boundary, in flight together
+  const bool pipe = total > 0 && total <= chunk && total + 256 < ((uint64_t)1 << 31) && tiles.size() >= 2 && pipeline_wanted(c, p);
+  // (the first half's slots are rounded up to 256, so the pair needs up to 255 more than one wave)
+  c->ensure_paths((uint32_t)(std::min<uint64_t>(chunk, std::max<uint64_t>(total, 1)) + (pipe ? 256u : 0u)));
   chunk = std::min<uint32_t>(chunk, c->cap);
   WaveState P = c->state();
   if (p->flags & BLING_PASS_NO_MIS_CULL) P.mis_cull = 0u;
+  c->last_pass_waves = 0;
   hipStream_t s = c->stream;
   HIPCHK(hipMemsetAsync(c->counters.p, 0, sizeof(Counters), s));
   hipEvent_t e0, e1;
@@ -599,6 +626,72 @@ int render(bling_ctx* c, const bling_pass_params* p, float* film_dev, bling_stat
   size_t t0 = 0;
   std::vector<TileDesc> batch;
   c->tiles_dev.alloc(std::max<size_t>(1, tiles.size()));
+  if (pipe) {
+    // the cut: the first tile boundary at or past half of the paths (total > 0: the first half is not empty)
+    size_t cut = 0;
+    uint32_t nh[2] = {0u, 0u};
+    while (cut + 1 < tiles.size() && 2 * (uint64_t)nh[0] < total) nh[0] += tiles[cut++].count;
+    uint32_t maxc[2] = {0u, 0u}, run[2] = {0u, 0u};
+    for (size_t k = 0; k < tiles.size(); ++k) {      // each half's sample ids start at 0
+      const int h = k < cut ? 0 : 1;
+      TileDesc t = tiles[k];
+      t.offset = run[h]; run[h] += t.count;
+      maxc[h] = std::max(maxc[h], t.count);
+      batch.push_back(t);
+    }
+    nh[1] = run[1];
+    const uint32_t cap_a = (nh[0] + 255u) & ~255u;
+    if ((uint64_t)cap_a + nh[1] > c->cap) throw std::runtime_error("half-waves exceed the path capacity");
+    c->ensure_half_streams();
+    const hipStream_t hs[2] = {c->half_stream[0], c->half_stream[1]};
+    HalfWave H[2] = {{c->state_half(0, cap_a), nh[0], hs[0], c->tiles_dev.p, (unsigned)cut, maxc[0]},
+                     {c->state_half(1, cap_a), nh[1], hs[1], c->tiles_dev.p + cut, (unsigned)(tiles.size() - cut), maxc[1]}};
+    for (auto& h : H) h.W.mis_cull = P.mis_cull;
+    HIPCHK(hipMemcpyAsync(c->tiles_dev.p, batch.data(), batch.size() * sizeof(TileDesc), hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(eb0, s));
+    // the halves start after everything enqueued so far (the tile table, the counters' reset, the
+    // previous pass's film), and the film waits for each of them
+    HIPCHK(hipEventRecord(c->half_fork, s));
+    try {
+      for (int h = 0; h < 2; ++h) HIPCHK(hipStreamWaitEvent(hs[h], c->half_fork, 0));
+      launches += (uint64_t)run_wave_pair(c, H, p->seed, p->pass_index, stats_on, &tm);
+      for (int h = 0; h < 2; ++h) {
+        HIPCHK(hipEventRecord(c->half_done[h], hs[h]));
+        HIPCHK(hipStreamWaitEvent(s, c->half_done[h], 0));
+        if (h == 1) HIPCHK(hipEventRecord(eb1, s));
+        launch_film(c, H[h].W, H[h].td, H[h].n_tiles, film_dev, timg ? timg + (h ? cut : 0) * slot_floats : nullptr);
+      }
+      HIPCHK(hipEventRecord(ef1, s));
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(s));
+    } catch (...) {
+      // an error between the fork and the join: nothing of the halves may still run on the context's
+      // buffers when the caller sees it (the next pass, or ensure_paths, would reuse or free them)
+      for (int h = 0; h < 2; ++h) (void)hipStreamSynchronize(hs[h]);
+      (void)hipStreamSynchronize(s);
+      throw;
+    }
+    samples += (uint64_t)nh[0] + nh[1];
+    c->last_pass_waves = -2;            // bling_debug_pass_results: two half-waves in flight together
+    c->last_n[0] = nh[0]; c->last_n[1] = nh[1]; c->last_off[1] = cap_a;
+    t0 = tiles.size();
+    // ms_film: the second half's film only (the first half's runs beside the second half's last
+    // launches); ms_bounce: from the halves' start to the end of the later one
+    float a = 0.f, b = 0.f;
+    HIPCHK(hipEventElapsedTime(&a, eb0, eb1));
+    HIPCHK(hipEventElapsedTime(&b, eb1, ef1));
+    ms_bounce += a; ms_film += b;
+    for (auto* ev : {&tm.ev, &tm.ev_shade}) {
+      for (size_t k = 0; k + 1 < ev->size(); k += 2) {
+        float m = 0.f;
+        HIPCHK(hipEventElapsedTime(&m, (*ev)[k], (*ev)[k + 1]));
+        if (ev == &tm.ev) { ms_closest += m; ++n_closest; } else { ms_shade += m; ++n_shade; }
+        (void)hipEventDestroy((*ev)[k]); (void)hipEventDestroy((*ev)[k + 1]);
+      }
+      ev->clear();
+    }
+  }
+  int n_waves = 0;
   while (t0 < tiles.size()) {
     batch.clear();
     uint32_t off = 0, maxc = 0;
@@ -613,12 +706,14 @@ int render(bling_ctx* c, const bling_pass_params* p, float* film_dev, bling_stat
     HIPCHK(hipEventRecord(eb0, s));
     launches += (uint64_t)run_wave(c, P, off, p->seed, p->pass_index, stats_on, &tm);
     HIPCHK(hipEventRecord(eb1, s));
-    launch_film(c, P, (unsigned)batch.size(), film_dev, timg ? timg + t0 * slot_floats : nullptr);
+    launch_film(c, P, c->tiles_dev.p, (unsigned)batch.size(), film_dev, timg ? timg + t0 * slot_floats : nullptr);
     HIPCHK(hipEventRecord(ef1, s));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));   // the tile table is reused by the next chunk
     samples += off;
     t0 = t1;
+    c->last_pass_waves = ++n_waves;
+    c->last_n[0] = off; c->last_n[1] = 0; c->last_off[1] = 0;
     float a = 0.f, b = 0.f;
     HIPCHK(hipEventElapsedTime(&a, eb0, eb1));
     HIPCHK(hipEventElapsedTime(&b, eb1, ef1));
@@ -1141,6 +1236,64 @@ int bling_debug_set_mis_cull(bling_ctx* c, int on) {
   c->mis_cull_off = !on;
   for (auto& p : c->peers) p->mis_cull_off = !on;
   return BLING_OK;
+}
+
+int bling_debug_set_pipeline(bling_ctx* c, int mode) {
+  if (!c || mode < -1 || mode > 1) { g_err = "bad argument"; return BLING_EINVAL; }
+  c->pipeline_mode = mode;
+  for (auto& p : c->peers) p->pipeline_mode = mode;
+  return BLING_OK;
+}
+
+int bling_debug_pass_results(bling_ctx* c, float* out, size_t cap, size_t* n, int* waves) {
+  return guarded([&] {
+    if (!c || !n) throw std::invalid_argument("null argument");
+    if (!c->peers.empty()) throw std::invalid_argument("single-device contexts only");
+    if (waves) *waves = c->last_pass_waves;
+    if (c->last_pass_waves != 1 && c->last_pass_waves != -2) throw std::invalid_argument("the last pass did not keep its samples' results");
+    *n = (size_t)c->last_n[0] + c->last_n[1];
+    if (!out) return BLING_OK;
+    if (cap < *n) throw std::invalid_argument("capacity below the pass's samples");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpy(out, c->result.p, (size_t)c->last_n[0] * sizeof(float4), hipMemcpyDeviceToHost));
+    if (c->last_n[1])
+      HIPCHK(hipMemcpy(out + 4 * (size_t)c->last_n[0], c->result.p + c->last_off[1], (size_t)c->last_n[1] * sizeof(float4),
+                       hipMemcpyDeviceToHost));
+    return BLING_OK;
+  });
+}
+
+int bling_debug_compact(bling_ctx* c, const uint8_t* flags, const uint32_t* queue_in, size_t n, size_t capacity, int fused,
+                        uint32_t* queues_out, uint32_t* qcount_out) {
+  return guarded([&] {
+    if (!c || !flags || !queue_in || !queues_out || !qcount_out) throw std::invalid_argument("null argument");
+    if (capacity == 0 || n > capacity || capacity > (1u << 24)) throw std::invalid_argument("bad queue length or capacity");
+    HIPCHK(hipSetDevice(c->device));
+    c->ensure_paths((uint32_t)capacity);
+    WaveState W = c->state();
+    hipStream_t s = c->stream;
+    const uint32_t nb = (uint32_t)((capacity + COMPACT_CHUNK - 1) / COMPACT_CHUNK);
+    // every flag past the queue's end set, every output word poisoned: neither may show in the result
+    HIPCHK(hipMemsetAsync(W.qflag, 0xFF, c->cap, s));
+    HIPCHK(hipMemsetAsync(c->qmem.p, 0xEE, (size_t)6 * c->cap * sizeof(uint32_t), s));
+    if (n) {
+      HIPCHK(hipMemcpyAsync(W.qflag, flags, n, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(W.queue[Q_SHADE0], queue_in, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    }
+    k_reset_queues<<<1, 64, 0, s>>>(W.qcount, (uint32_t)n);
+    k_compact_count<<<nb, 256, 0, s>>>(W, nb, 0);
+    k_compact_scan<<<1, 1024, 0, s>>>(W, nb, 0, fused);
+    k_compact_scatter<<<nb, 256, 0, s>>>(W, nb, 0, fused);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpy(qcount_out, W.qcount, QC_N * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const int ids[5] = {Q_SHADE0, Q_SHADE1, Q_CLOSEST, Q_ANY, Q_RESOLVE};
+    const size_t at[5] = {0, 1, 2, 4, 5};
+    for (int k = 0; k < 5; ++k)
+      HIPCHK(hipMemcpy(queues_out + at[k] * capacity, W.queue[ids[k]], (ids[k] == Q_CLOSEST ? 2 : 1) * capacity * sizeof(uint32_t),
+                       hipMemcpyDeviceToHost));
+    return BLING_OK;
+  });
 }
 
 int bling_debug_mis_culled(bling_ctx* c, uint64_t* out) {

@@ -110,6 +110,18 @@ struct bling_ctx {
   using WaveState = bd::WaveState;
   int device = 0;
   hipStream_t stream = nullptr;
+  // a pipelined pass (core.hip render): one stream per half-wave, the event they start after and the
+  // events the film waits on; created by the first such pass
+  hipStream_t half_stream[2] = {nullptr, nullptr};
+  hipEvent_t half_fork = nullptr, half_done[2] = {nullptr, nullptr};
+  // the shade grid of a half-wave: four blocks per CU, the blocks k_shade keeps resident (one round of
+  // blocks, not grid_for's two).  Measured on C2 with the half traversal grids, pass ms pipelined /
+  // single in one process: 1 block per CU 70.1 / 65.8, 2: 61.6 / 64.4, 3: 61.5 / 65.7, 4: 60.7 / 65.4,
+  // grid_for's 8: 60.8 / 65.7 (profiles/r09_c2_pipeline_ab.jsonl)
+  unsigned half_shade_blocks = 4 * 256;
+  int pipeline_mode = -1;       // bling_debug_set_pipeline: -1 the profile's default, 0 never, 1 wherever legal
+  int last_pass_waves = 0;      // waves of the last render pass on this device; -2: two half-waves in flight together
+  uint32_t last_n[2] = {0, 0}, last_off[2] = {0, 0};   // the samples of its last wave (or two half-waves) in result
   bool has_scene = false;
   DevScene S{};
   // scene memory
@@ -197,6 +209,11 @@ struct bling_ctx {
   ~bling_ctx() {
     peers.clear();                          // each peer frees its memory on its own device
     (void)hipSetDevice(device);
+    for (int h = 0; h < 2; ++h) {
+      if (half_stream[h]) (void)hipStreamDestroy(half_stream[h]);
+      if (half_done[h]) (void)hipEventDestroy(half_done[h]);
+    }
+    if (half_fork) (void)hipEventDestroy(half_fork);
     if (stream) (void)hipStreamDestroy(stream);
   }
 
@@ -229,9 +246,23 @@ struct bling_ctx {
     result.alloc(cap); img.alloc(cap);
     qmem.alloc((size_t)6 * cap);     // SHADE0, SHADE1, CLOSEST (2 cap), ANY, RESOLVE
     march.alloc((size_t)2 * cap);    // reused: closest-queue results, then any-queue results
-    qcount.alloc(QC_N);              // the Q_N queue lengths and the culled MIS count (QC_MISCULL)
+    qcount.alloc(2 * kQcountStride);   // per half-wave: the Q_N queue lengths and the culled MIS count (QC_MISCULL)
     qflag.alloc(cap);
-    blk.alloc((size_t)5 * (cap / COMPACT_CHUNK + 2));   // [nb][4], totals [4], culled [nb]
+    blk.alloc((size_t)5 * (cap / COMPACT_CHUNK + 4) + 4);   // per half-wave: [nb][4], totals [4], culled [nb]
+  }
+  static constexpr uint32_t kQcountStride = 8;
+  static_assert(kQcountStride >= QC_N, "a half-wave's counters");
+  void ensure_half_streams() {
+    for (int h = 0; h < 2; ++h) {
+      if (!half_stream[h]) HIPCHK(hipStreamCreateWithFlags(&half_stream[h], hipStreamNonBlocking));
+      if (!half_done[h]) HIPCHK(hipEventCreateWithFlags(&half_done[h], hipEventDisableTiming));
+    }
+    if (!half_fork) {
+      HIPCHK(hipEventCreateWithFlags(&half_fork, hipEventDisableTiming));
+      int cus = 0;
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
+        half_shade_blocks = 4u * (unsigned)cus;
+    }
   }
   WaveState state() {
     WaveState W{};
@@ -254,6 +285,33 @@ struct bling_ctx {
     W.sb = counters.p ? counters.p->sb : nullptr;
     W.cap = cap;
     W.mis_cull = (mis_cull_ok && !mis_cull_off) ? 1u : 0u;   // bling_render_pass* clears it on BLING_PASS_NO_MIS_CULL
+    return W;
+  }
+  // Half-wave h of a pipelined pass (Path only): the first cap_a slots of every buffer are half 0's,
+  // the rest half 1's, so the two hold what one wave holds.  cap_a is a multiple of 256: every half's
+  // arrays keep the alignment their 16-byte accesses need (flag words, compaction rows).
+  WaveState state_half(int h, uint32_t cap_a) {
+    WaveState W = state();
+    const size_t o = h ? cap_a : 0;
+    const uint32_t ch = h ? cap - cap_a : cap_a;
+    for (PathSet* P : {&W.cur, &W.nxt}) {
+      P->org += o; P->dir += o; P->hit += o; P->meta += o; P->mdir += o; P->mhit += o; P->fm += o; P->occ += o;
+      P->fac += o; P->rtex += o; P->sh_o += o; P->sh_d += o;
+      P->T += 4 * o; P->L += 4 * o;
+      if (P->Tn) { P->Tn += 4 * o; P->lsc += 4 * o; P->bsc += 4 * o; }
+    }
+    W.img += o; W.result += o;
+    W.march_t += 2 * o;
+    uint32_t* q = qmem.p + 6 * o;
+    W.queue[Q_SHADE0] = q;
+    W.queue[Q_SHADE1] = q + ch;
+    W.queue[Q_CLOSEST] = q + 2 * (size_t)ch;
+    W.queue[Q_ANY] = q + 4 * (size_t)ch;
+    W.queue[Q_RESOLVE] = q + 5 * (size_t)ch;
+    W.qcount += h * kQcountStride;
+    W.qflag += o;
+    if (h) W.blk += ((size_t)5 * (cap_a / COMPACT_CHUNK + 2) + 3) & ~(size_t)3;
+    W.cap = ch;
     return W;
   }
 };
@@ -309,6 +367,17 @@ namespace bcore {
 // Drive one wave of n freshly generated paths to completion (Path.hs:41-87 for every path).
 // Queue lengths stay on the device: every launch is a grid-stride loop that reads the live count
 // itself, so the host never synchronises inside the loop.
+// One half-wave of a pipelined pass: its state, paths and stream, and its tiles (n_tiles entries of
+// the pass's tile table on the device, the largest of max_tile samples) for the camera rays.
+struct HalfWave {
+  WaveState W;
+  uint32_t n;
+  hipStream_t s;
+  const TileDesc* td;
+  unsigned n_tiles;
+  uint32_t max_tile;
+};
+
 struct WaveTiming {
   bool on = false;
   std::vector<hipEvent_t> ev;      // pairs around each k_trace_closest launch
@@ -322,13 +391,14 @@ inline unsigned grid_for(uint32_t items) {
 
 // Grid of a persistent (grid-stride, lane-refill) kernel: exactly the blocks that are co-resident
 // on the device, so no second partial round of blocks idles most CUs at the tail.
+// div = 2: half of them, for a half-wave of a pipelined pass that shares the device with the other's.
 template <class K>
-unsigned persistent_grid(K kernel, size_t lds, uint32_t items) {
+unsigned persistent_grid(K kernel, size_t lds, uint32_t items, unsigned div = 1) {
   int dev = 0, cus = 0, per_cu = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     cus = 256;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-  const uint32_t cap = (uint32_t)(cus * per_cu);
+  const uint32_t cap = std::max(1u, (uint32_t)(cus * per_cu) / std::max(1u, div));
   return std::max(1u, std::min((items + 255u) / 256u, cap));
 }
 
@@ -337,6 +407,10 @@ unsigned persistent_grid(K kernel, size_t lds, uint32_t items) {
 // the build runs them in parallel) and sppm_pass.hip.
 template <uint32_t F>
 int run_wave_prof(bling_ctx* c, const WaveState& W, uint32_t n, uint32_t seed, uint32_t pass, bool stats, WaveTiming* tm);
+// The same for a pipelined pass (core_wave.h run_wave_pair_t): the two half-waves h[0], h[1], from
+// their camera rays on.
+template <uint32_t F>
+int run_wave_pair_prof(bling_ctx* c, const HalfWave* h, uint32_t seed, uint32_t pass, bool stats, WaveTiming* tm);
 template <uint32_t F>
 void launch_trace_prof(bling_ctx* c, const float* rays, uint32_t n, int any_hit, float* t, uint32_t* prim, float* bary);
 template <uint32_t F>

@@ -58,27 +58,29 @@ static __global__ __launch_bounds__(256) void k_trace(const DevScene* __restrict
 template <uint32_t F, bool STATS, bool ALLL>
 struct TraceLaunch {
   bling_ctx* c;
+  hipStream_t s;
   bool pkt, bf;
   unsigned gc, ga;
   size_t lds() const { return use_bvh4<F>() ? c->lds_trace4 : c->lds_trace; }
   size_t pkt_lds() const { return sizeof(DevShape) * c->S.lds4_shapes; }   // packet_lds
-  TraceLaunch(bling_ctx* c_, uint32_t n) : c(c_), pkt(false), bf(false), gc(1), ga(1) {
+  // div = 2: the grids of a half-wave of a pipelined pass (half of the co-resident blocks each)
+  TraceLaunch(bling_ctx* c_, uint32_t n, hipStream_t s_, unsigned div = 1) : c(c_), s(s_), pkt(false), bf(false), gc(1), ga(1) {
     if constexpr (!(F & FT_FRACTAL)) {
       bf = c->S.bf_tris + c->S.bf_shapes > 0;
       pkt = !bf && c->S.pkt_n > 0;
       if (bf) {
-        gc = persistent_grid(k_trace_closest_bf<F, STATS>, 0, 2 * n);
-        ga = persistent_grid(k_trace_any_bf<F, STATS>, 0, n);
+        gc = persistent_grid(k_trace_closest_bf<F, STATS>, 0, 2 * n, div);
+        ga = persistent_grid(k_trace_any_bf<F, STATS>, 0, n, div);
         return;
       }
       if (pkt) {
-        gc = persistent_grid(k_trace_closest_pkt<F, STATS>, pkt_lds(), 2 * n);
-        ga = persistent_grid(k_trace_any_pkt<F, STATS>, pkt_lds(), n);
+        gc = persistent_grid(k_trace_closest_pkt<F, STATS>, pkt_lds(), 2 * n, div);
+        ga = persistent_grid(k_trace_any_pkt<F, STATS>, pkt_lds(), n, div);
         return;
       }
     }
-    gc = persistent_grid(k_trace_closest<F, STATS, ALLL>, lds(), 2 * n);
-    ga = persistent_grid(k_trace_any<F, STATS, ALLL>, lds(), n);
+    gc = persistent_grid(k_trace_closest<F, STATS, ALLL>, lds(), 2 * n, div);
+    ga = persistent_grid(k_trace_any<F, STATS, ALLL>, lds(), n, div);
     if constexpr (use_bvh4<F>()) {
       if ((size_t)std::max(gc, ga) * 256 > c->S.stack4_lanes && c->S.stack4_need > c->S.stack4_lds)
         throw std::runtime_error("BVH4 stack overflow rows sized for fewer lanes than the traversal grid");
@@ -86,17 +88,17 @@ struct TraceLaunch {
   }
   void closest(const WaveState& W) const {
     if constexpr (!(F & FT_FRACTAL)) {
-      if (bf) { k_trace_closest_bf<F, STATS><<<gc, 256, 0, c->stream>>>(c->dscene.p, W, c->counters.p); return; }
-      if (pkt) { k_trace_closest_pkt<F, STATS><<<gc, 256, pkt_lds(), c->stream>>>(c->dscene.p, W, c->counters.p); return; }
+      if (bf) { k_trace_closest_bf<F, STATS><<<gc, 256, 0, s>>>(c->dscene.p, W, c->counters.p); return; }
+      if (pkt) { k_trace_closest_pkt<F, STATS><<<gc, 256, pkt_lds(), s>>>(c->dscene.p, W, c->counters.p); return; }
     }
-    k_trace_closest<F, STATS, ALLL><<<gc, 256, lds(), c->stream>>>(c->dscene.p, W, c->counters.p);
+    k_trace_closest<F, STATS, ALLL><<<gc, 256, lds(), s>>>(c->dscene.p, W, c->counters.p);
   }
   void any(const WaveState& W) const {
     if constexpr (!(F & FT_FRACTAL)) {
-      if (bf) { k_trace_any_bf<F, STATS><<<ga, 256, 0, c->stream>>>(c->dscene.p, W, c->counters.p); return; }
-      if (pkt) { k_trace_any_pkt<F, STATS><<<ga, 256, pkt_lds(), c->stream>>>(c->dscene.p, W, c->counters.p); return; }
+      if (bf) { k_trace_any_bf<F, STATS><<<ga, 256, 0, s>>>(c->dscene.p, W, c->counters.p); return; }
+      if (pkt) { k_trace_any_pkt<F, STATS><<<ga, 256, pkt_lds(), s>>>(c->dscene.p, W, c->counters.p); return; }
     }
-    k_trace_any<F, STATS, ALLL><<<ga, 256, lds(), c->stream>>>(c->dscene.p, W, c->counters.p);
+    k_trace_any<F, STATS, ALLL><<<ga, 256, lds(), s>>>(c->dscene.p, W, c->counters.p);
   }
 };
 
@@ -113,28 +115,43 @@ void shade_dl_launch(unsigned gs, hipStream_t s, const DevScene* d, const WaveSt
   k_shade_dl<F><<<gs, 256, 0, s>>>(d, W, qin, seed, pass, C);
 }
 
+// The launches of one wave of Path paths, vertex by vertex, in two stages per depth: trace(d) --
+// closest-hit, any-hit, staging -- and shade(d) -- the shade launch and the compaction of its flags.
+// A wave runs them in turn on its stream; a pipelined pass (run_wave_pair_t) interleaves two waves.
 template <uint32_t F, bool STATS, bool ALLL>
-int run_wave_t(bling_ctx* c, WaveState W, uint32_t n, uint32_t seed, uint32_t pass, WaveTiming* tm) {
-  hipStream_t s = c->stream;
-  const DevScene* d = c->dscene.p;
-  Counters* C = c->counters.p;
-  const unsigned gs = grid_for(n);
-  const TraceLaunch<F, STATS, ALLL> tl(c, n);
-  const uint32_t nb = (n + COMPACT_CHUNK - 1) / COMPACT_CHUNK;
+struct WaveRun {
+  bling_ctx* c;
+  WaveState W;
+  hipStream_t s;
+  uint32_t seed, pass;
+  WaveTiming* tm;
+  const DevScene* d;
+  Counters* C;
+  unsigned gs;
+  TraceLaunch<F, STATS, ALLL> tl;
+  uint32_t nb;
   // Mandelbulb scenes: each traversal launch is preceded by the march of its queue (k_march), whose
   // results the traversal kernels read at the fractal leaf; Julia scenes march inside the traversal
   bool premarch = false;
   unsigned gmc = 1, gma = 1;
-  if constexpr ((F & FT_FRACTAL) != 0) {
-    // (k_march_jobs keeps 16-bit loop counters: deeper iteration counts march in the traversal)
-    premarch = W.march_t != nullptr && c->S.fractal.kind == BLING_FRACTAL_MANDELBULB && c->S.fractal.iterations < 32767;
-    if (premarch) {
-      gmc = persistent_grid(k_march_jobs<F, STATS, false>, 0, 2 * n);
-      gma = persistent_grid(k_march_jobs<F, STATS, true>, 0, n);
+  int launches = 0;
+  // grid_div = 2: a half-wave of a pipelined pass, whose persistent grids take half of the device
+  WaveRun(bling_ctx* c_, const WaveState& W_, uint32_t n, hipStream_t s_, uint32_t seed_, uint32_t pass_, WaveTiming* tm_,
+          unsigned grid_div = 1, unsigned shade_blocks = 0)
+      : c(c_), W(W_), s(s_), seed(seed_), pass(pass_), tm(tm_), d(c_->dscene.p), C(c_->counters.p),
+        gs(shade_blocks ? std::min(shade_blocks, grid_for(n)) : grid_for(n)), tl(c_, n, s_, grid_div),
+        nb((n + COMPACT_CHUNK - 1) / COMPACT_CHUNK) {
+    if constexpr ((F & FT_FRACTAL) != 0) {
+      // (k_march_jobs keeps 16-bit loop counters: deeper iteration counts march in the traversal)
+      premarch = W.march_t != nullptr && c->S.fractal.kind == BLING_FRACTAL_MANDELBULB && c->S.fractal.iterations < 32767;
+      if (premarch) {
+        gmc = persistent_grid(k_march_jobs<F, STATS, false>, 0, 2 * n, grid_div);
+        gma = persistent_grid(k_march_jobs<F, STATS, true>, 0, n, grid_div);
+      }
     }
+    if (!premarch) W.march_t = nullptr;
   }
-  if (!premarch) W.march_t = nullptr;
-  auto march = [&](bool anyq) {
+  void march(bool anyq) {
     if constexpr ((F & FT_FRACTAL) != 0) {
       if (!premarch) return;
       if (anyq) k_march_jobs<F, STATS, true><<<gma, 256, 0, s>>>(d, W, C);
@@ -142,51 +159,40 @@ int run_wave_t(bling_ctx* c, WaveState W, uint32_t n, uint32_t seed, uint32_t pa
     } else {
       (void)anyq;
     }
-  };
-  int launches = 0;
-  for (int depth = 0; depth <= c->S.max_depth; ++depth) {
-    if (tm && tm->on) {                // the closest-hit queries' time includes their march
+  }
+  // a pair of events around the launches fn enqueues, when the pass is timed
+  template <class Fn>
+  void timed(std::vector<hipEvent_t>& ev, Fn&& fn) {
+    if (tm && tm->on) {
       hipEvent_t a, b;
       HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
-      tm->ev.push_back(a); tm->ev.push_back(b);
+      ev.push_back(a); ev.push_back(b);
       HIPCHK(hipEventRecord(a, s));
-      march(false);
-      tl.closest(W);
+      fn();
       HIPCHK(hipEventRecord(b, s));
     } else {
-      march(false);
-      tl.closest(W);
+      fn();
     }
+  }
+  void trace(int depth) {
+    timed(tm->ev, [&] { march(false); tl.closest(W); });   // the closest-hit queries' time includes their march
     if (depth > 0) {
       march(true);
       tl.any(W);
       ++launches;
     }
-    int qin = depth & 1;
-    k_stage<<<1, 64, 0, s>>>(W.qcount, qin, depth, C, 1);
-    if (depth > 0) {
-      // resolve(d - 1) + shade(d) over the resolve list of d - 1 (wavefront.h k_shade<F, true>):
-      // reads the current set at the listed slots, writes vertex d to the next set at its entries
-      if (tm && tm->on) {
-        hipEvent_t a, b;
-        HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
-        tm->ev_shade.push_back(a); tm->ev_shade.push_back(b);
-        HIPCHK(hipEventRecord(a, s));
-        shade_launch<F, true>(gs, s, d, W, depth, qin, seed, pass, C);
-        HIPCHK(hipEventRecord(b, s));
-      } else {
-        shade_launch<F, true>(gs, s, d, W, depth, qin, seed, pass, C);
-      }
-    } else if (tm && tm->on) {        // depth 0 is timed with the fused launches (ms_shade)
-      hipEvent_t a, b;
-      HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
-      tm->ev_shade.push_back(a); tm->ev_shade.push_back(b);
-      HIPCHK(hipEventRecord(a, s));
-      shade_launch<F, false>(gs, s, d, W, depth, qin, seed, pass, C);
-      HIPCHK(hipEventRecord(b, s));
-    } else {
-      shade_launch<F, false>(gs, s, d, W, depth, qin, seed, pass, C);
-    }
+    k_stage<<<1, 64, 0, s>>>(W.qcount, depth & 1, depth, C, 1);
+    launches += 2;
+  }
+  void shade(int depth) {
+    const int qin = depth & 1;
+    // depth > 0: resolve(d - 1) + shade(d) over the resolve list of d - 1 (wavefront.h k_shade<F, true>):
+    // reads the current set at the listed slots, writes vertex d to the next set at its entries;
+    // depth 0 is timed with the fused launches (ms_shade)
+    timed(tm->ev_shade, [&] {
+      if (depth > 0) shade_launch<F, true>(gs, s, d, W, depth, qin, seed, pass, C);
+      else shade_launch<F, false>(gs, s, d, W, depth, qin, seed, pass, C);
+    });
     std::swap(W.cur, W.nxt);           // the queues built next index the set just written
     if (depth < c->S.max_depth) {      // shade at maxDepth finalises every path: nothing to queue
       k_compact_count<<<nb, 256, 0, s>>>(W, nb, qin);
@@ -194,9 +200,45 @@ int run_wave_t(bling_ctx* c, WaveState W, uint32_t n, uint32_t seed, uint32_t pa
       k_compact_scatter<<<nb, 256, 0, s>>>(W, nb, qin, 1);
       launches += 3;
     }
-    launches += 3;
+    ++launches;
   }
-  return launches;
+  void stage(int k) { if (k & 1) shade(k >> 1); else trace(k >> 1); }
+  // a half-wave's start: its queue counters and the camera rays of its tiles
+  void raygen(const HalfWave& h) {
+    k_reset_queues<<<1, 64, 0, s>>>(W.qcount, h.n);
+    k_raygen<<<dim3((h.max_tile + 255) / 256, h.n_tiles), 256, 0, s>>>(d, W, h.td, seed, pass);
+  }
+};
+
+template <uint32_t F, bool STATS, bool ALLL>
+int run_wave_t(bling_ctx* c, WaveState W, uint32_t n, uint32_t seed, uint32_t pass, WaveTiming* tm) {
+  WaveTiming none;
+  WaveRun<F, STATS, ALLL> r(c, W, n, c->stream, seed, pass, tm ? tm : &none);
+  for (int k = 0; k < 2 * (c->S.max_depth + 1); ++k) r.stage(k);
+  return r.launches;
+}
+
+// A pipelined pass: two half-waves A and B, each on its own stream, enqueued stage by stage with B
+// one stage behind A, so that in the steady state A's shade launch (HBM bound) and B's traversal
+// launches (LDS / issue bound) are in flight together and the reverse.  The halves share nothing but
+// the scene and the counters; each stream orders its own wave, and the host never waits.
+// B's queue reset and camera rays are enqueued after A's depth-0 shade launch.  Each persistent
+// traversal grid takes half of the co-resident blocks; the shade grid is bling_ctx::half_shade_blocks.
+template <uint32_t F, bool STATS, bool ALLL>
+int run_wave_pair_t(bling_ctx* c, const HalfWave* h, uint32_t seed, uint32_t pass, WaveTiming* tm) {
+  WaveTiming none;
+  WaveRun<F, STATS, ALLL> a(c, h[0].W, h[0].n, h[0].s, seed, pass, tm ? tm : &none, 2, c->half_shade_blocks);
+  WaveRun<F, STATS, ALLL> b(c, h[1].W, h[1].n, h[1].s, seed, pass, tm ? tm : &none, 2, c->half_shade_blocks);
+  const int stages = 2 * (c->S.max_depth + 1);
+  a.raygen(h[0]);
+  a.stage(0);
+  for (int k = 1; k < stages; ++k) {
+    a.stage(k);
+    if (k == 1) b.raygen(h[1]);
+    b.stage(k - 1);
+  }
+  b.stage(stages - 1);
+  return a.launches + b.launches;
 }
 
 // DirectLighting: one tree node per path per step.  The number of steps depends on the specular
@@ -208,7 +250,7 @@ int run_wave_dl_t(bling_ctx* c, WaveState W, uint32_t n, uint32_t seed, uint32_t
   const DevScene* d = c->dscene.p;
   Counters* C = c->counters.p;
   const unsigned gs = grid_for(n), gr = grid_for(n);
-  const TraceLaunch<F, STATS, ALLL> tl(c, n);
+  const TraceLaunch<F, STATS, ALLL> tl(c, n, s);
   const uint32_t nb = (n + COMPACT_CHUNK - 1) / COMPACT_CHUNK;
   const int max_steps = (1 << c->S.max_depth);        // a tree of depth < maxDepth has < 2^maxDepth nodes
   W.march_t = nullptr;                                // the traversal kernels march themselves
@@ -267,6 +309,15 @@ int run_wave_prof(bling_ctx* c, const WaveState& W, uint32_t n, uint32_t seed, u
 }
 
 template <uint32_t F>
+int run_wave_pair_prof(bling_ctx* c, const HalfWave* h, uint32_t seed, uint32_t pass, bool stats, WaveTiming* tm) {
+  const bool all = use_bvh4<F>() ? c->lds_all4 : c->lds_all;
+  if (c->S.integrator == BLING_INTEGRATOR_DIRECT) throw std::runtime_error("a pipelined pass runs the Path integrator only");
+  if (all)
+    return stats ? run_wave_pair_t<F, true, true>(c, h, seed, pass, tm) : run_wave_pair_t<F, false, true>(c, h, seed, pass, tm);
+  return stats ? run_wave_pair_t<F, true, false>(c, h, seed, pass, tm) : run_wave_pair_t<F, false, false>(c, h, seed, pass, tm);
+}
+
+template <uint32_t F>
 void launch_trace_prof(bling_ctx* c, const float* rays, uint32_t n, int any_hit, float* t, uint32_t* prim, float* bary) {
   unsigned blocks = (n + 255) / 256;
   hipStream_t s = c->stream;
@@ -286,6 +337,8 @@ void launch_trace_prof(bling_ctx* c, const float* rays, uint32_t n, int any_hit,
   namespace bcore {                                                                                               \
   template <> int run_wave_prof<kProfiles[K]>(bling_ctx*, const WaveState&, uint32_t, uint32_t, uint32_t, bool,   \
                                               WaveTiming*) { throw std::runtime_error("profile stubbed in this experiment build"); } \
+  template <> int run_wave_pair_prof<kProfiles[K]>(bling_ctx*, const HalfWave*, uint32_t, uint32_t, bool, WaveTiming*) { \
+    throw std::runtime_error("profile stubbed in this experiment build"); }                                       \
   template <> void launch_trace_prof<kProfiles[K]>(bling_ctx*, const float*, uint32_t, int, float*, uint32_t*, float*) { \
     throw std::runtime_error("profile stubbed in this experiment build"); }                                       \
   }
@@ -297,6 +350,7 @@ void launch_trace_prof(bling_ctx* c, const float* rays, uint32_t n, int any_hit,
   namespace bcore {                                                                                               \
   template int run_wave_prof<kProfiles[K]>(bling_ctx*, const WaveState&, uint32_t, uint32_t, uint32_t, bool,      \
                                            WaveTiming*);                                                          \
+  template int run_wave_pair_prof<kProfiles[K]>(bling_ctx*, const HalfWave*, uint32_t, uint32_t, bool, WaveTiming*);  \
   template void launch_trace_prof<kProfiles[K]>(bling_ctx*, const float*, uint32_t, int, float*, uint32_t*, float*); \
   }
 // split profiles: this unit compiles the pipeline without the shading kernels, whose launch wrappers

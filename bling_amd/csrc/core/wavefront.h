@@ -56,7 +56,16 @@ constexpr int shade_min_waves() {
        : ((F & (FT_GLASS | FT_SUBSTRATE | FT_BUMP)) ? 2
        : (F == (FT_MATTE | FT_AREA | FT_TRIS) ? BLING_CORNELL_SHADE_WAVES : ((F & FT_TRIS) ? 3 : 1)));
 }
-#define SHADE_OCC __attribute__((amdgpu_waves_per_eu(shade_min_waves<F>(), 8)))
+// The cornell profile's cap, for experiment builds only: BLING_CORNELL_SHADE_MAX_WAVES=2 measures its
+// k_shade at half occupancy, as beside a half traversal grid (profiles/r09_c2_halfocc_ab.jsonl).
+#ifndef BLING_CORNELL_SHADE_MAX_WAVES
+#define BLING_CORNELL_SHADE_MAX_WAVES 8
+#endif
+template <uint32_t F>
+constexpr int shade_max_waves() { return F == (FT_MATTE | FT_AREA | FT_TRIS) ? BLING_CORNELL_SHADE_MAX_WAVES : 8; }
+template <uint32_t F>
+constexpr int shade_occ_min() { return shade_min_waves<F>() < shade_max_waves<F>() ? shade_min_waves<F>() : shade_max_waves<F>(); }
+#define SHADE_OCC __attribute__((amdgpu_waves_per_eu(shade_occ_min<F>(), shade_max_waves<F>())))
 // The fractal profiles' closest-hit kernel (the paired march) sits just above the 168 VGPRs of
 // three waves per SIMD; it is held to three.  The all-LDS BVH4 kernel (ALLL: small scenes, no global
 // fallback) is held to eight (70 -> 64 VGPRs; A/B on C2, profiles/r02_ab_occupancy_s5.txt: closest
@@ -1552,11 +1561,12 @@ static __global__ void k_stage(uint32_t* qcount, int qin, int depth, Counters* C
   unsigned long long closest = qcount[Q_CLOSEST], any = qcount[Q_ANY];
   // MIS queries of d - 1 that direct_setup answered (mis_cull_test): queries all the same, not queued
   const unsigned long long culled = qcount[QC_MISCULL];
-  if (depth == 0) C->cam += alive; else C->cont += alive;
-  C->mis += closest - alive + culled;
-  C->mis_culled += culled;
-  C->shadow += any;
-  C->vertices += alive;
+  // adds, not read-modify-write stores: two half-waves of a pipelined pass stage concurrently
+  atomicAdd(depth == 0 ? &C->cam : &C->cont, alive);
+  atomicAdd(&C->mis, closest - alive + culled);
+  atomicAdd(&C->mis_culled, culled);
+  atomicAdd(&C->shadow, any);
+  atomicAdd(&C->vertices, alive);
 }
 
 // ------------------------------------------------------------------ queue compaction
@@ -1565,28 +1575,58 @@ static __global__ void k_stage(uint32_t* qcount, int qin, int depth, Counters* C
 // three small launches instead of same-address atomics from every wave (those serialise across
 // the 8 XCDs and cost milliseconds per bounce).  Closest queue = all MIS entries, then all
 // continuation entries, each in shade-queue order (paths stay in raygen order: coherent rays).
+// The flags are read as 16-byte words: one uint4 per lane covers a wave's 1024 entries, lane l holding
+// entries 16 l .. 16 l + 15 (one coalesced 1-KiB load in place of sixteen byte loads per lane).
+// Entries at or past n read as 0.  The flag array's length is a multiple of 16 (ensure_paths), so a
+// word whose first entry lies below n lies inside it.
+DEV uint4 wave_flag_words(const uint8_t* __restrict__ flag, uint32_t wb, uint32_t n) {
+  const uint32_t e0 = wb + 16u * (threadIdx.x & 63u);
+  uint4 f = make_uint4(0u, 0u, 0u, 0u);
+  if (e0 < n) {
+    f = *reinterpret_cast<const uint4*>(flag + e0);
+    const uint32_t live = n - e0;                             // entries of this lane below n
+    auto keep = [live](uint32_t lo) {                        // mask of the word holding entries lo .. lo + 3
+      return live <= lo ? 0u : (live >= lo + 4u ? ~0u : (1u << (8u * (live - lo))) - 1u);
+    };
+    f.x &= keep(0u); f.y &= keep(4u); f.z &= keep(8u); f.w &= keep(12u);
+  }
+  return f;
+}
+// the lane's entries with flag bit c set
+DEV uint32_t flag_count(const uint4& f, int c) {
+  const uint32_t m = 0x01010101u << c;
+  return (uint32_t)(__popc(f.x & m) + __popc(f.y & m) + __popc(f.z & m) + __popc(f.w & m));
+}
+DEV uint32_t wave_sum_u32(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// a wave's count of each of the first NC flag bits over its 1024 entries: per-lane popcounts, two
+// counts (at most 1024 each) to a word, summed over the wave
 template <int NC>
-DEV void wave_counts(const uint8_t* __restrict__ flag, uint32_t wb, uint32_t n, uint32_t cnt[NC]) {
-  const uint32_t lane = threadIdx.x & 63u;
+DEV void wave_counts(const uint4& f, uint32_t cnt[NC]) {
 #pragma unroll
-  for (int c = 0; c < NC; ++c) cnt[c] = 0u;
-  for (uint32_t k = 0; k < 16; ++k) {
-    uint32_t e = wb + k * 64u + lane;
-    uint32_t f = e < n ? flag[e] : 0u;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) cnt[c] += (uint32_t)__popcll(__ballot((f >> c) & 1u));
+  for (int c = 0; c < NC; c += 2) {
+    uint32_t v = flag_count(f, c);
+    if (c + 1 < NC) v |= flag_count(f, c + 1) << 16;
+    v = wave_sum_u32(v);
+    cnt[c] = v & 0xFFFFu;
+    if (c + 1 < NC) cnt[c + 1] = v >> 16;
   }
 }
 
 // blk: per block the four scattered counts [nb][4], the totals' row [4], then the blocks' culled
-// counts [nb] (summed by the scan, never scattered)
+// counts [nb] (summed by the scan, never scattered).  Only the rows of the live blocks, those that
+// hold an entry below qcount[qin], are written here and read by the scan and the scatter.
 static __global__ __launch_bounds__(256) void k_compact_count(WaveState W, uint32_t nb, int qin) {
   __shared__ uint32_t s[4][QF_COUNTS];
   const uint32_t n = W.qcount[qin];
+  if (blockIdx.x * COMPACT_CHUNK >= n) return;               // whole block past the queue
   const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
   const uint32_t wb = blockIdx.x * COMPACT_CHUNK + w * 1024u;
   uint32_t cnt[QF_COUNTS];
-  wave_counts<QF_COUNTS>(W.qflag, wb, n, cnt);
+  wave_counts<QF_COUNTS>(wave_flag_words(W.qflag, wb, n), cnt);
   if (lane == 0) for (int c = 0; c < QF_COUNTS; ++c) s[w][c] = cnt[c];
   __syncthreads();
   if (threadIdx.x < QF_COUNTS) {
@@ -1596,55 +1636,81 @@ static __global__ __launch_bounds__(256) void k_compact_count(WaveState W, uint3
   }
 }
 
-// one block of 1024: exclusive scan of the per-block counts; queue lengths for the next launches
+// one block of 1024: exclusive scan of the live blocks' counts (ceil(qcount[qin] / 4096) rows, read
+// here, not the wave's capacity); queue lengths for the next launches.  Each thread sums a run of
+// consecutive rows, a wave scans its 64 sums with shuffles, and the 16 wave totals meet in LDS: one
+// barrier.
 // fused: the next shade input (qin ^ 1) is the resolve list, and Q_RESOLVE's counter carries the
 // continuation count (k_stage); otherwise the next shade input is the continuation list.
 static __global__ __launch_bounds__(1024) void k_compact_scan(WaveState W, uint32_t nb, int qin, int fused) {
-  __shared__ uint32_t s[1024][4];
+  __shared__ uint32_t wtot[16][4];
   __shared__ uint32_t culled[16];                            // per wave
-  const uint32_t t = threadIdx.x;
-  const uint32_t seg = (nb + 1023u) / 1024u, b0 = t * seg, b1 = min(nb, b0 + seg);
+  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+  const uint32_t n = W.qcount[qin];
+  const uint32_t live = min(nb, (n + COMPACT_CHUNK - 1u) / COMPACT_CHUNK);
+  const uint32_t seg = (live + 1023u) / 1024u, b0 = min(live, t * seg), b1 = min(live, b0 + seg);
+  uint4* rows = reinterpret_cast<uint4*>(W.blk);             // a block's four counts: one 16-B row
   uint32_t sum[4] = {0u, 0u, 0u, 0u}, cull = 0u;
   for (uint32_t b = b0; b < b1; ++b) {
-    for (int c = 0; c < 4; ++c) sum[c] += W.blk[4 * b + c];
+    const uint4 r = rows[b];
+    sum[0] += r.x; sum[1] += r.y; sum[2] += r.z; sum[3] += r.w;
     cull += W.blk[4 * nb + 4 + b];
   }
-  for (int c = 0; c < 4; ++c) s[t][c] = sum[c];
-  cull = (uint32_t)wave_sum_u64((unsigned long long)cull);   // the culled total needs no scan
-  if ((t & 63u) == 0u) culled[t >> 6] = cull;
-  __syncthreads();
-  for (uint32_t off = 1; off < 1024; off <<= 1) {          // Hillis-Steele inclusive scan
-    uint32_t v[4];
-    for (int c = 0; c < 4; ++c) v[c] = t >= off ? s[t - off][c] : 0u;
-    __syncthreads();
-    for (int c = 0; c < 4; ++c) s[t][c] += v[c];
-    __syncthreads();
+  uint32_t inc[4];                                           // inclusive scan over the wave's lanes
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    uint32_t v = sum[c];
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t u = __shfl_up(v, o, 64);
+      if (lane >= (uint32_t)o) v += u;
+    }
+    inc[c] = v;
   }
+  cull = wave_sum_u32(cull);                                 // the culled total needs no scan
+  if (lane == 63u) for (int c = 0; c < 4; ++c) wtot[w][c] = inc[c];
+  if (lane == 0u) culled[w] = cull;
+  __syncthreads();
   uint32_t run[4];
-  for (int c = 0; c < 4; ++c) run[c] = s[t][c] - sum[c];
-  for (uint32_t b = b0; b < b1; ++b)
-    for (int c = 0; c < 4; ++c) { uint32_t x = W.blk[4 * b + c]; W.blk[4 * b + c] = run[c]; run[c] += x; }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    uint32_t base = 0u;
+    for (uint32_t v = 0; v < w; ++v) base += wtot[v][c];
+    inc[c] += base;
+    run[c] = inc[c] - sum[c];
+  }
+  for (uint32_t b = b0; b < b1; ++b) {
+    const uint4 r = rows[b];
+    rows[b] = make_uint4(run[0], run[1], run[2], run[3]);
+    run[0] += r.x; run[1] += r.y; run[2] += r.z; run[3] += r.w;
+  }
   if (t == 1023) {
-    const uint32_t tr = s[t][0], ta = s[t][1], tm = s[t][2], tc = s[t][3];
+    const uint32_t tr = inc[0], ta = inc[1], tm = inc[2], tc = inc[3];
     W.blk[4 * nb + 0] = tm;                                   // MIS total = start of the continuation part
     W.qcount[Q_RESOLVE] = fused ? tc : tr;
     W.qcount[Q_ANY] = ta;
     W.qcount[Q_CLOSEST] = tm + tc;
     W.qcount[qin ^ 1] = fused ? tr : tc;
     uint32_t tq = 0u;
-    for (int w = 0; w < 16; ++w) tq += culled[w];
+    for (int v = 0; v < 16; ++v) tq += culled[v];
     W.qcount[QC_MISCULL] = tq;
   }
 }
 
+// The scatter keeps its stores coalesced: a wave's flag words go through LDS, and lane l then takes
+// entry 64 k + l of round k as before, so the lanes of a store write consecutive queue positions
+// (lane-owned runs of 16 entries would spread every store over 64 lines).
 static __global__ __launch_bounds__(256) void k_compact_scatter(WaveState W, uint32_t nb, int qin, int fused) {
   __shared__ uint32_t s[4][4];
+  __shared__ uint4 fw[4][64];
   const uint32_t n = W.qcount[qin];
   const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
   const uint32_t wb = blockIdx.x * COMPACT_CHUNK + w * 1024u;
   if (blockIdx.x * COMPACT_CHUNK >= n) return;               // whole block past the queue
   uint32_t cnt[4];
-  wave_counts<4>(W.qflag, wb, n, cnt);
+  const uint4 f16 = wave_flag_words(W.qflag, wb, n);
+  fw[w][lane] = f16;
+  wave_counts<4>(f16, cnt);
   if (lane == 0) for (int c = 0; c < 4; ++c) s[w][c] = cnt[c];
   __syncthreads();
   uint32_t off[4];
@@ -1659,12 +1725,14 @@ static __global__ __launch_bounds__(256) void k_compact_scatter(WaveState W, uin
   uint32_t* qc = W.queue[Q_CLOSEST];
   uint32_t* qn = fused ? nullptr : W.queue[qin ^ 1];
   const unsigned long long below = (1ull << lane) - 1ull;
+  const uint8_t* fb = reinterpret_cast<const uint8_t*>(&fw[w][0]);
   for (uint32_t k = 0; k < 16; ++k) {
     uint32_t e = wb + k * 64u + lane;
-    uint32_t f = 0u, i = 0u;
+    uint32_t i = 0u;
     // Path (fused): the next queues list the entries themselves -- the shade launch wrote each
     // vertex to slot e of the next set; DirectLighting (in place): the sample ids
-    if (e < n) { f = W.qflag[e]; i = fused ? e : qi[e]; }
+    const uint32_t f = fb[k * 64u + lane];                   // 0 at and past n (wave_flag_words)
+    if (e < n) i = fused ? e : qi[e];
     unsigned long long m0 = __ballot(f & QF_RESOLVE), m1 = __ballot(f & QF_ANY);
     unsigned long long m2 = __ballot(f & QF_MIS), m3 = __ballot(f & QF_CONT);
     if (f & QF_RESOLVE) qr[off[0] + __popcll(m0 & below)] = i;

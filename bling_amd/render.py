@@ -122,6 +122,38 @@ class Context:
         """bling_debug_set_mis_cull: switch the MIS cull for every later call (sample_li included)."""
         _check(_ffi.hip().bling_debug_set_mis_cull(self._h, 1 if on else 0))
 
+    def set_pipeline(self, mode: int):
+        """bling_debug_set_pipeline: -1 the scene profile's default, 0 never, 1 wherever a pass can run
+        as two half-waves on two streams (the pass flag PASS_NO_PIPELINE still wins)."""
+        _check(_ffi.hip().bling_debug_set_pipeline(self._h, int(mode)))
+
+    def pass_results(self):
+        """bling_debug_pass_results: the last pass's per-sample results, [n, 4] (X, Y, Z, 1 or zeros) in
+        tile order, and how it ran: the number of waves, or -2 for two half-waves in flight together."""
+        n, waves = C.c_size_t(), C.c_int()
+        _check(_ffi.hip().bling_debug_pass_results(self._h, None, 0, C.byref(n), C.byref(waves)))
+        out = np.zeros((int(n.value), 4), np.float32)
+        _check(_ffi.hip().bling_debug_pass_results(self._h, _ffi.f32ptr(out), out.shape[0], C.byref(n), C.byref(waves)))
+        return out, int(waves.value)
+
+    def compact(self, flags: np.ndarray, queue_in: np.ndarray, capacity: int | None = None, fused: bool = True):
+        """bling_debug_compact: one compaction of the flag bytes over the input queue.  Returns
+        ({"shade0", "shade1", "closest", "any", "resolve"} -> the raw queue arrays, qcount[6])."""
+        flags = np.ascontiguousarray(flags, np.uint8)
+        queue_in = np.ascontiguousarray(queue_in, np.uint32)
+        n = int(flags.size)
+        cap = int(capacity if capacity is not None else max(n, 1))
+        fl = flags if n else np.zeros(1, np.uint8)
+        qi = queue_in if n else np.zeros(1, np.uint32)
+        out = np.zeros(6 * cap, np.uint32)
+        qc = np.zeros(6, np.uint32)
+        _check(_ffi.hip().bling_debug_compact(self._h, fl.ctypes.data_as(C.POINTER(C.c_uint8)), qi.ctypes.data_as(_ffi.c_u32p),
+                                              n, cap, 1 if fused else 0, out.ctypes.data_as(_ffi.c_u32p),
+                                              qc.ctypes.data_as(_ffi.c_u32p)))
+        q = {"shade0": out[:cap], "shade1": out[cap:2 * cap], "closest": out[2 * cap:4 * cap], "any": out[4 * cap:5 * cap],
+             "resolve": out[5 * cap:]}
+        return q, qc
+
     def stream_bytes(self) -> dict:
         """bling_debug_stream_bytes: k_shade's path-state bytes of the last pass per stream,
         {name: (read, written)} (BLING_STREAM_STATS builds only)."""

@@ -70,6 +70,12 @@ typedef struct bling_pass_params {
  * measurements and the tests.  BLING_DEBUG_VERTEX builds never cull (they record every vertex's MIS
  * hit distance, record 29), with or without this bit. */
 #define BLING_PASS_NO_MIS_CULL     16u
+/* Render the pass as one wave on one stream.  By default a pass whose paths fit one wave and that has
+ * at least two tiles runs, for the scene profiles where that measured faster, as
+ * two half-waves cut at a tile boundary, each on its own stream, so that one half's shading and the
+ * other's traversal share the device.  Every sample's arithmetic is the same either way; only the
+ * order of the film's float additions differs.  The switch is for A/B measurements and the tests. */
+#define BLING_PASS_NO_PIPELINE     32u
 
 typedef struct bling_stats {
     uint64_t camera_samples;   /* paths started                                               */
@@ -87,6 +93,12 @@ typedef struct bling_stats {
     uint64_t node_visits;      /* BVH2 nodes fetched (64 B each)                               */
     uint64_t tri_tests;        /* triangle tests (48 B records)                                */
     uint64_t shape_tests;      /* instanced shape / fractal tests                              */
+    /* ms_closest and ms_shade are sums over launches of each launch's own elapsed time.  In a
+       pipelined pass (see BLING_PASS_NO_PIPELINE) the two half-waves' launches overlap, so the sums
+       count shared time twice and no longer add up to ms_bounce; ms_total is the yardstick.  In such
+       a pass ms_bounce runs from the halves' start to the end of the later one, which includes the
+       first half's film (it runs beside the second half's last launches), and ms_film is the second
+       half's film alone. */
     double   ms_closest;       /* BLING_PASS_KERNEL_TIMING: summed k_trace_closest launch times */
     uint64_t closest_launches; /* BLING_PASS_KERNEL_TIMING: k_trace_closest launches timed      */
     uint64_t march_ticks;      /* BLING_PASS_TRAVERSAL_STATS: Mandelbulb march iterations (one
@@ -322,6 +334,26 @@ int bling_debug_mis_culled(bling_ctx* ctx, uint64_t* out);
  * walks all its MIS rays, as BLING_PASS_NO_MIS_CULL does for one pass; on = 1 (the default) restores
  * the cull.  Per-sample radiance is summed by no atomics, so it can be compared bit for bit. */
 int bling_debug_set_mis_cull(bling_ctx* ctx, int on);
+
+/* Diagnostics: which passes of the context run pipelined (BLING_PASS_NO_PIPELINE still wins): -1 the
+ * scene profile's default, 0 none, 1 every pass for which it is legal (Path integrator, one wave, at
+ * least two tiles, the traversal stack in LDS). */
+int bling_debug_set_pipeline(bling_ctx* ctx, int mode);
+/* Diagnostics: the per-sample results (X, Y, Z, 1, or zeros for a dropped sample: what addSample
+ * receives) of the context's last bling_render_pass*, in the pass's tile order, and how it ran:
+ * *waves = the number of waves run one after another, or -2 for two half-waves in flight together.
+ * Only a pass of one wave or of two half-waves keeps them all (else BLING_EINVAL).  No float
+ * atomics sum them, so two passes can be compared bit for bit.  *n receives the sample count; out
+ * (4 floats per sample, cap samples; may be NULL) is written when cap suffices. */
+int bling_debug_pass_results(bling_ctx* ctx, float* out, size_t cap, size_t* n, int* waves);
+/* Diagnostics: one order-preserving compaction (the k_compact_* launches between two path vertices)
+ * of n shade-queue entries with the given flag bytes (QF_* bits: 1 resolve, 2 shadow ray, 4 MIS ray,
+ * 8 continuation, 16 culled MIS query) and input queue words, launched over capacity >= n entries.
+ * queues_out: 6 * capacity words -- the two shade queues (capacity each), the closest-hit queue
+ * (2 * capacity), the any-hit queue and the resolve list; qcount_out: their five lengths and the
+ * culled count.  fused: as the Path integrator compacts (entries) or as DirectLighting (sample ids). */
+int bling_debug_compact(bling_ctx* ctx, const uint8_t* flags, const uint32_t* queue_in, size_t n, size_t capacity,
+                        int fused, uint32_t* queues_out, uint32_t* qcount_out);
 
 /* The uploaded scene's acceleration / kernel plan as one JSON object (BVH2 and BVH4 depth and
  * sizes, the BVH4 stack bound, the LDS plans, the packet walk, the in-line shadow test), written
