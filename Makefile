@@ -7,6 +7,7 @@
 #   bling_amd/_lib/bling              C++ command-line renderer (host front end)
 #   bling_amd/_lib/libbling_mathcheck.so  exhaustive device check of common/fast_cr.h (tests)
 #   tests/ref/_build/liblt_ref.so     CPU restatement of the light tracer over the oracle (tests)
+#   tests/ref/_build/libbd_ref.so     CPU restatement of the bidirectional integrator over the oracle (tests)
 
 HIPCC    ?= /opt/rocm/bin/hipcc
 CXX      ?= g++
@@ -43,12 +44,13 @@ HIPFLAGS  := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -ffp-contract=off -fno-
              -Wno-unused-result -munsafe-fp-atomics
 
 all: $(LIBDIR)/libbling_host.so $(LIBDIR)/libbling_hip.so $(ORADIR)/liboracle.so $(LIBDIR)/bling \
-     $(LIBDIR)/libbling_mathcheck.so $(LTRDIR)/liblt_ref.so
+     $(LIBDIR)/libbling_mathcheck.so $(LTRDIR)/liblt_ref.so $(LTRDIR)/libbd_ref.so
 
 host: $(LIBDIR)/libbling_host.so
 oracle: $(ORADIR)/liboracle.so
 core: $(LIBDIR)/libbling_hip.so
 ltref: $(LTRDIR)/liblt_ref.so
+bdref: $(LTRDIR)/libbd_ref.so
 
 $(LIBDIR)/libbling_host.so: $(HOST_SRC) $(HOST_HDR)
 	@mkdir -p $(LIBDIR)
@@ -63,11 +65,19 @@ $(LTRDIR)/liblt_ref.so: tests/ref/lighttracer_ref.cpp $(ORA_SRC) $(ORA_HDR)
 	@mkdir -p $(LTRDIR)
 	$(CXX) $(HOSTFLAGS) -Wno-subobject-linkage -fopenmp -shared -o $@ tests/ref/lighttracer_ref.cpp
 
+# the bidirectional integrator's restatement, built the same way; tests only
+$(LTRDIR)/libbd_ref.so: tests/ref/bidir_ref.cpp $(ORA_SRC) $(ORA_HDR)
+	@mkdir -p $(LTRDIR)
+	$(CXX) $(HOSTFLAGS) -Wno-subobject-linkage -fopenmp -shared -o $@ tests/ref/bidir_ref.cpp
+
 # one object per unit (core, sppm driver, one per kernel feature profile) so make -j compiles the
 # kernel instantiations in parallel
 $(OBJDIR)/%.o: bling_amd/csrc/core/% $(CORE_HDR)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(DEFS) $(STUBDEF) -c -o $@ $<
+
+# the all-features bidir units include the driver unit's source
+$(OBJDIR)/bidir_pass_walk.hip.o $(OBJDIR)/bidir_pass_connect.hip.o: bling_amd/csrc/core/bidir_pass.hip
 
 $(LIBDIR)/libbling_hip.so: $(CORE_OBJ)
 	@mkdir -p $(LIBDIR)
@@ -92,4 +102,4 @@ variant: $(CORE_OBJ)
 clean:
 	rm -rf $(LIBDIR) $(ORADIR) $(LTRDIR) build
 
-.PHONY: all host oracle core ltref clean variant
+.PHONY: all host oracle core ltref bdref clean variant

@@ -128,7 +128,7 @@ HIP_SYMBOLS = ["bling_create", "bling_scene_upload", "bling_scene_validate", "bl
                "bling_trace", "bling_trace_device", "bling_sample_li", "bling_sample_li_vertices", "bling_pass_tile_layout",
                "bling_film_add_tiles", "bling_film_add_shards", "bling_sppm_pass", "bling_sppm_pixel_stats", "bling_sppm_reset",
                "bling_render", "bling_debug_stream_bytes", "bling_debug_scene_info", "bling_debug_mis_culled", "bling_debug_set_mis_cull", "bling_debug_set_pipeline", "bling_debug_pass_results", "bling_debug_compact", "bling_debug_sppm_hitpoints", "bling_debug_sppm_buckets",
-               "bling_light_pass", "bling_debug_light_records", "bling_destroy", "bling_last_error", "bling_version"]
+               "bling_light_pass", "bling_debug_light_records", "bling_debug_bidir_terms", "bling_destroy", "bling_last_error", "bling_version"]
 
 
 class Progress(C.Structure):
@@ -197,6 +197,10 @@ def hip() -> C.CDLL:
         lib.bling_debug_light_records.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                   C.POINTER(LightRecord), C.c_size_t, C.POINTER(C.c_size_t)]
         lib.bling_debug_light_records.restype = C.c_int
+        if hasattr(lib, "bling_debug_bidir_terms"):   # older experiment builds lack it
+            lib.bling_debug_bidir_terms.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.c_size_t,
+                                                    c_f32p, C.POINTER(C.c_int32)]
+            lib.bling_debug_bidir_terms.restype = C.c_int
         lib.bling_debug_scene_info.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
         lib.bling_debug_scene_info.restype = C.c_int
         if hasattr(lib, "bling_debug_mis_culled"):    # older experiment builds lack it

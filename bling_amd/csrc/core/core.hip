@@ -104,6 +104,11 @@ void validate_scene(const bling_scene_desc* d) {
     // the tree is walked depth-first with one parked sibling per level (k_shade_dl): bound it
     if (d->config.max_depth < 1 || d->config.max_depth > kMaxDlDepth)
       throw std::invalid_argument("directLighting maxDepth outside [1, " + std::to_string(kMaxDlDepth) + "]");
+  } else if (d->config.integrator == BLING_INTEGRATOR_BIDIR) {
+    // both subpaths' specular masks are 16-bit words, the vertex buffers 2 maxDepth records (bidir.h)
+    if (d->config.max_depth < 1 || d->config.max_depth > BD_MAX_DEPTH)
+      throw std::invalid_argument("bidir maxDepth outside [1, " + std::to_string(BD_MAX_DEPTH) + "]");
+    if (d->config.sample_depth < 0) throw std::invalid_argument("bidir sampleDepth < 0");
   } else if (d->config.integrator != BLING_INTEGRATOR_PATH) {
     throw std::invalid_argument("unknown surface integrator");
   }
@@ -457,6 +462,7 @@ void upload_scene(bling_ctx* c, const bling_scene_desc* d) {
   S.max_depth = cfg.max_depth; S.sample_depth = cfg.sample_depth;
   S.integrator = cfg.integrator;
   if (S.integrator == BLING_INTEGRATOR_DIRECT) S.n1d = S.n2d = 2 * cfg.max_depth;   // DirectLighting.hs:17-18
+  else if (S.integrator == BLING_INTEGRATOR_BIDIR) { S.n1d = 12 * cfg.sample_depth + 1; S.n2d = 9 * cfg.sample_depth + 2; }   // BidirPath.hs:44-48
   else { S.n1d = 4 * cfg.sample_depth; S.n2d = 3 * cfg.sample_depth; }              // Path.hs:26-28
   if (cfg.spp > (1 << 24)) throw std::runtime_error("more than 2^24 samples per pixel (the sampler's permutation, counter_rng.h)");
   S.fd_spp = FastDiv::make((uint32_t)std::max(1, cfg.spp));
@@ -492,7 +498,7 @@ void upload_scene(bling_ctx* c, const bling_scene_desc* d) {
 bool pipeline_wanted(const bling_ctx* c, const bling_pass_params* p) {
   if (BLING_DEBUG_VERTEX || BLING_STREAM_STATS) return false;
   if (p->flags & BLING_PASS_NO_PIPELINE) return false;
-  if (c->S.integrator == BLING_INTEGRATOR_DIRECT) return false;
+  if (c->S.integrator != BLING_INTEGRATOR_PATH) return false;
   if (c->S.stack4_need > c->S.stack4_lds) return false;
   if (c->pipeline_mode >= 0) return c->pipeline_mode != 0;
   return profile_of(c->features) == kProfiles[0];
@@ -700,11 +706,17 @@ int render(bling_ctx* c, const bling_pass_params* p, float* film_dev, bling_stat
       TileDesc t = tiles[t1]; t.offset = off; off += t.count; maxc = std::max(maxc, t.count); batch.push_back(t); ++t1;
     }
     HIPCHK(hipMemcpyAsync(c->tiles_dev.p, batch.data(), batch.size() * sizeof(TileDesc), hipMemcpyHostToDevice, s));
-    dim3 g((maxc + 255) / 256, (unsigned)batch.size());
-    k_reset_queues<<<1, 64, 0, s>>>(P.qcount, off);
-    k_raygen<<<g, 256, 0, s>>>(c->dscene.p, P, c->tiles_dev.p, p->seed, p->pass_index);
-    HIPCHK(hipEventRecord(eb0, s));
-    launches += (uint64_t)run_wave(c, P, off, p->seed, p->pass_index, stats_on, &tm);
+    if (S.integrator == BLING_INTEGRATOR_BIDIR) {
+      HIPCHK(hipEventRecord(eb0, s));
+      launches += (uint64_t)bidir_wave(c, P, c->tiles_dev.p, (unsigned)batch.size(), maxc, nullptr, off, p->seed,
+                                           p->pass_index, nullptr);
+    } else {
+      dim3 g((maxc + 255) / 256, (unsigned)batch.size());
+      k_reset_queues<<<1, 64, 0, s>>>(P.qcount, off);
+      k_raygen<<<g, 256, 0, s>>>(c->dscene.p, P, c->tiles_dev.p, p->seed, p->pass_index);
+      HIPCHK(hipEventRecord(eb0, s));
+      launches += (uint64_t)run_wave(c, P, off, p->seed, p->pass_index, stats_on, &tm);
+    }
     HIPCHK(hipEventRecord(eb1, s));
     launch_film(c, P, c->tiles_dev.p, (unsigned)batch.size(), film_dev, timg ? timg + t0 * slot_floats : nullptr);
     HIPCHK(hipEventRecord(ef1, s));
@@ -1007,7 +1019,7 @@ int bling_render_pass(bling_ctx* c, const bling_pass_params* p, float* film_out,
 }
 
 static int sample_li_impl(bling_ctx* c, uint32_t seed, uint32_t pass_index, const int32_t* samples, size_t n, float* L_out,
-                   float* img_out, bling_stats* st, float* vtx_out) {
+                   float* img_out, bling_stats* st, float* vtx_out, float* terms_out = nullptr, int32_t* lens_out = nullptr) {
   return guarded([&] {
     if (!c || !samples || !L_out) throw std::invalid_argument("null argument");
     if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
@@ -1036,12 +1048,20 @@ static int sample_li_impl(bling_ctx* c, uint32_t seed, uint32_t pass_index, cons
     }
     hipStream_t s = c->stream;
     HIPCHK(hipMemsetAsync(c->counters.p, 0, sizeof(Counters), s));
-    unsigned blocks = (unsigned)((n + 255) / 256);
-    k_reset_queues<<<1, 64, 0, s>>>(P.qcount, (uint32_t)n);
-    k_raygen_list<<<blocks, 256, 0, s>>>(c->dscene.p, P, list.p, (uint32_t)n, seed, pass_index);
-    run_wave(c, P, (uint32_t)n, seed, pass_index, false);
+    DBuf<float> terms;
+    if (S.integrator == BLING_INTEGRATOR_BIDIR) {
+      if (terms_out) terms.alloc(n * 48);
+      bidir_wave(c, P, nullptr, 0u, 0u, list.p, (uint32_t)n, seed, pass_index, terms.p);
+    } else {
+      unsigned blocks = (unsigned)((n + 255) / 256);
+      k_reset_queues<<<1, 64, 0, s>>>(P.qcount, (uint32_t)n);
+      k_raygen_list<<<blocks, 256, 0, s>>>(c->dscene.p, P, list.p, (uint32_t)n, seed, pass_index);
+      run_wave(c, P, (uint32_t)n, seed, pass_index, false);
+    }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
+    if (terms.p) HIPCHK(hipMemcpy(terms_out, terms.p, n * 48 * sizeof(float), hipMemcpyDeviceToHost));
+    if (lens_out && c->bidir.info.p) HIPCHK(hipMemcpy(lens_out, c->bidir.info.p, n * sizeof(uint4), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(L_out, lfull.p, n * 16 * sizeof(float), hipMemcpyDeviceToHost));
     if (vtx_out) HIPCHK(hipMemcpy(vtx_out, vtx.p, vtx.n * sizeof(float), hipMemcpyDeviceToHost));
     if (img_out) {
@@ -1056,6 +1076,7 @@ static int sample_li_impl(bling_ctx* c, uint32_t seed, uint32_t pass_index, cons
       st->camera_samples = n;
       st->rays_camera = hc.cam; st->rays_continuation = hc.cont; st->rays_mis = hc.mis; st->rays_shadow = hc.shadow;
       st->dropped_samples = hc.dropped;
+      if (S.integrator == BLING_INTEGRATOR_BIDIR) st->path_vertices = hc.vertices;
     }
     return BLING_OK;
   });
@@ -1315,6 +1336,17 @@ int bling_debug_stream_bytes(bling_ctx* c, uint64_t* out, size_t n, size_t* n_st
 int bling_sample_li(bling_ctx* c, uint32_t seed, uint32_t pass_index, const int32_t* samples, size_t n, float* L_out,
                     float* img_out, bling_stats* st) {
   return sample_li_impl(c, seed, pass_index, samples, n, L_out, img_out, st, nullptr);
+}
+
+int bling_debug_bidir_terms(bling_ctx* c, uint32_t seed, uint32_t pass_index, const int32_t* samples, size_t n,
+                            float* terms_out, int32_t* lens_out) {
+  if (!terms_out || !lens_out) { g_err = "null argument"; return BLING_EINVAL; }
+  if (c && c->has_scene && c->S.integrator != BLING_INTEGRATOR_BIDIR) {
+    g_err = "the uploaded scene's integrator is not bidir";
+    return BLING_EINVAL;
+  }
+  std::vector<float> L(16 * std::max<size_t>(n, 1));
+  return sample_li_impl(c, seed, pass_index, samples, n, L.data(), nullptr, nullptr, nullptr, terms_out, lens_out);
 }
 
 int bling_sample_li_vertices(bling_ctx* c, uint32_t seed, uint32_t pass_index, const int32_t* samples, size_t n,

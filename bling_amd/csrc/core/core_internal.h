@@ -20,6 +20,7 @@
 #include "wavefront.h"
 #include "sppm.h"
 #include "light_tracer.h"
+#include "bidir.h"
 
 namespace bcore {
 using namespace bd;
@@ -66,6 +67,11 @@ constexpr uint64_t kPathFixedBytes = 16 + 8 + 6 * 4 + 1 + 4 + 2 * 4;   // ... + 
 // weight) per level below maxDepth
 constexpr uint64_t kDlSlotBytes = 16 + 16 + 64;
 constexpr int kMaxDlDepth = 16;
+// The bidirectional integrator keeps no path set; per sample it stores 2 maxDepth vertex records (ray,
+// direction, hit, wo: 16 B each; alpha 64 B), maxDepth direct and maxDepth connection spectra, the le
+// term and the lengths / masks (bidir.h BdBufs)
+constexpr uint64_t kBdVertexBytes = 4 * 16 + 64;
+inline uint64_t bd_sample_bytes(int md) { return (uint64_t)md * (2 * kBdVertexBytes + 2 * 64) + 64 + 16; }
 
 // SPPM renderer state (sppm.h): hit points, hash grid and the per-pixel statistics that persist
 // across passes (reset by a scene upload or bling_sppm_reset)
@@ -88,6 +94,25 @@ struct SppmState {
     for (auto* b : {&r2, &nacc, &splat, &film, &kd_mr, &kd_c}) b->free();
     hp_key.free(); grid.free(); ctr.free(); tiles.free();
     ready = false; hp_cap = items_cap = 0;
+  }
+};
+
+// Bidirectional integrator state (bidir.h): the vertex buffers of one wave, sized for the largest wave a
+// bidir scene of this context asked for (not for the path capacity an earlier scene left behind)
+struct BidirState {
+  DBuf<float4> vorg, vdir, vhit, vwo, valpha, ld, conn, le;
+  DBuf<uint4> info;
+  uint32_t cap = 0;
+  int md = 0;
+  void alloc(uint32_t n, int depth) {
+    cap = n; md = depth;
+    const size_t v = (size_t)2 * depth * n, e = (size_t)depth * n;
+    for (auto* b : {&vorg, &vdir, &vhit, &vwo}) b->alloc(v);
+    valpha.alloc(4 * v); ld.alloc(4 * e); conn.alloc(4 * e); le.alloc((size_t)4 * n); info.alloc(n);
+  }
+  void free_all() {
+    for (auto* b : {&vorg, &vdir, &vhit, &vwo, &valpha, &ld, &conn, &le}) b->free();
+    info.free(); cap = 0; md = 0;
   }
 };
 
@@ -197,6 +222,7 @@ struct bling_ctx {
   bling_render_config cfg{};    // the uploaded scene's renderer configuration
   SppmState sppm;
   LightState light;
+  BidirState bidir;
   bling_light_tracer lt{};      // the uploaded scene's light tracer block (photons per pass)
   // Multi-device fan-out (bling_create with n_devices > 1): one context per further device; every
   // device renders its share as tile images, the peers push theirs over xGMI into stage, and the
@@ -221,15 +247,25 @@ struct bling_ctx {
   // the uploaded scene's kernel profile keeps the three non-factored spectra per slot (wavefront.h
   // factored()); DirectLighting runs in place on one set
   bool want_spectra() const;
-  bool want_two_sets() const { return S.integrator != BLING_INTEGRATOR_DIRECT; }
+  bool want_two_sets() const { return S.integrator == BLING_INTEGRATOR_PATH; }
+  int want_bd_depth() const { return S.integrator == BLING_INTEGRATOR_BIDIR ? S.max_depth : 0; }
   uint64_t path_bytes() const {
     const uint64_t set_b = kSetBytes + (want_spectra() ? kSetSpectraBytes : 0);
-    return (want_two_sets() ? 2 : 1) * set_b + kPathFixedBytes + (want_dl_levels() ? 20 + kDlSlotBytes * want_dl_levels() : 0);
+    return (want_two_sets() ? 2 : 1) * set_b + kPathFixedBytes + (want_dl_levels() ? 20 + kDlSlotBytes * want_dl_levels() : 0) +
+           (want_bd_depth() ? bd_sample_bytes(want_bd_depth()) : 0);
   }
 
   void ensure_paths(uint32_t n) {
     const int lv = want_dl_levels();
     const bool sp = want_spectra(), two = want_two_sets();
+    // the bidir vertex buffers follow the waves asked for, not cap, which never shrinks: after a large
+    // Path pass a bidir scene would otherwise allocate its 384 maxDepth + 80 bytes for every old slot
+    if (const int bdm = want_bd_depth()) {
+      const uint32_t need = (n + 255u) & ~255u;
+      if (bidir.md != bdm || bidir.cap < need) bidir.alloc(need, bdm);
+    } else if (bidir.cap) {
+      bidir.free_all();
+    }
     const bool relayout = lv != dl_levels || sp != sets_spectra || two != sets_two;
     if (n <= cap && !relayout) return;
     cap = std::max(cap, (n + 255u) & ~255u);
@@ -359,6 +395,7 @@ inline uint32_t profile_of(uint32_t need) {
 inline bool bling_ctx::want_spectra() const {
   bool full = true;
   bcore::with_profile(features, [&](auto prof) { full = !bd::factored<decltype(prof)::value>(); });
+  if (S.integrator == BLING_INTEGRATOR_BIDIR) return false;   // its kernels keep no path set (bidir.h)
   return full || S.integrator == BLING_INTEGRATOR_DIRECT;
 }
 
@@ -422,5 +459,12 @@ void sppm_init(bling_ctx* c);
 template <uint32_t F>
 uint32_t light_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, uint32_t first, uint32_t count, bool splat,
                       uint32_t rec_cap, bling_light_stats* st);
+// One wave of the bidirectional integrator (bidir_pass.hip): the n camera samples of the tile table
+// (tiles != nullptr, the largest tile of max_tile samples) or of the device list of (x, y, n) triples,
+// walked, connected and finished into W.img / W.result (and W.Lfull); terms != nullptr: 3 x 16 floats
+// per sample (ld, le, l).  The kernels exist for the cornell profile and for every feature (computed
+// textures included: a vertex's BSDF is rebuilt where it is used).  Returns the launches.
+int bidir_wave(bling_ctx* c, const WaveState& W, const TileDesc* tiles, unsigned n_tiles, uint32_t max_tile,
+               const int32_t* list, uint32_t n, uint32_t seed, uint32_t pass, float* terms);
 
 }  // namespace bcore

@@ -254,6 +254,18 @@ class Context:
                                    _ffi.f32ptr(L), _ffi.f32ptr(img), C.byref(st)))
         return L, img, st
 
+    def bidir_terms(self, samples: np.ndarray, seed=DEFAULT_SEED, pass_index=0):
+        """bling_debug_bidir_terms: (terms (k, 3, 16) = ld, le, l of BidirPath's contrib, lens (k, 4) =
+        eye length, light length, eye and light specular masks) of the (x, y, n) samples."""
+        samples = np.ascontiguousarray(samples, np.int32)
+        n = samples.shape[0]
+        terms = np.zeros((n, 3, 16), np.float32)
+        lens = np.zeros((n, 4), np.int32)
+        lib = _ffi.hip()
+        _check(lib.bling_debug_bidir_terms(self._h, seed, pass_index, samples.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                                           _ffi.f32ptr(terms), lens.ctypes.data_as(C.POINTER(C.c_int32))))
+        return terms, lens
+
     def sample_li_vertices(self, samples: np.ndarray, seed=DEFAULT_SEED, pass_index=0):
         """sample_li plus the per-vertex debug records (include/bling.h BLING_DV_*): (L (k, 16),
         vtx (k, 16, 32)).  Needs the BLING_DEBUG_VERTEX build (BLING_HIP_VARIANT=dbg); the product

@@ -67,6 +67,20 @@ FEATURE_SCENES = {
 }
 
 
+# The bidirectional integrator (`integrator { bidir maxDepth N sampleDepth M }`, override bidir=N,M)
+# on scenes of this repository, for its parity tests (tests/test_bidir.py, tests/test_gpu_bidir.py).
+BIDIR_SCENES = {
+    "B1": BenchConfig("B1", "cornell-box.bling", "image=64,64;stratified=2,2;bidir=5,3", 0),   # one light, all-LDS profile
+    "B2": BenchConfig("B2", "cornell-box.bling", "image=64,64;stratified=2,2;bidir=1,1", 0),   # one vertex per subpath
+    "B3": BenchConfig("B3", "cornell-box.bling", "image=64,64;stratified=2,2;bidir=6,1", 0),   # most dimensions fresh
+    "B4": BenchConfig("B4", "direct-lighting.bling", "bidir=6,3", 0),                          # glass and mirror
+    "B5": BenchConfig("B5", "delta-lights.bling", "bidir=4,2", 0),                             # point / directional light rays
+    "B6": BenchConfig("B6", "sun-sky.bling", "image=48,27;bidir=5,3", 0),                      # infinite light, escaping eye rays
+    "B7": BenchConfig("B7", "procedural-textures.bling", "bidir=5,3", 0),                      # BSDFs rebuilt from computed textures
+    "B8": BenchConfig("B8", "cornell-box.bling", "image=48,48;stratified=2,2;bidir=5,3", 0),   # the film / wave / shard tests
+}
+
+
 class Job:
     """A parsed `.bling` job: RenderJob + the sampler/path renderer configuration."""
 
@@ -174,7 +188,7 @@ def parse_job(path: str, overrides: str | None = None) -> Job:
 
 
 def load_config(name: str, overrides_extra: str | None = None) -> Job:
-    c = CONFIGS[name] if name in CONFIGS else FEATURE_SCENES[name]
+    c = CONFIGS[name] if name in CONFIGS else BIDIR_SCENES[name] if name in BIDIR_SCENES else FEATURE_SCENES[name]
     ov = ";".join(x for x in (c.overrides, overrides_extra) if x)
     return Job(c.path, ov or None)
 

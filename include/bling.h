@@ -136,8 +136,11 @@ int bling_scene_upload(bling_ctx* ctx, const bling_scene_desc* desc);
 int bling_scene_validate(const bling_scene_desc* desc);
 
 /* Replaces: prender's onePass (Rendering.hs:127-140) for the `sampler` renderer with its `path`
- * (Integrator/Path.hs) or `directLighting` (Integrator/DirectLighting.hs) surface integrator,
- * selected by desc->config.integrator at upload (directLighting maxDepth must lie in [1, 16]).
+ * (Integrator/Path.hs), `directLighting` (Integrator/DirectLighting.hs) or `bidir`
+ * (Integrator/BidirPath.hs) surface integrator, selected by desc->config.integrator at upload
+ * (directLighting and bidir maxDepth must lie in [1, 16]; else BLING_EINVAL with the reason).  A bidir
+ * pass keeps 2 maxDepth vertex records per sample in flight and is cut into more waves accordingly;
+ * its ray counts are mapped as bling_sample_li describes.
  * film_out: host buffer of width*height*4 floats (W, X, Y, Z per pixel, Image.hs:64-71),
  * ACCUMULATED into (pass several passes to get the progressive sum); may be NULL.  On a multi-device
  * context the film holds the sum over all devices; stats sum the counts (times: the slowest device,
@@ -213,12 +216,26 @@ int bling_trace(bling_ctx* ctx, const float* rays_soa, size_t n, int any_hit,
 int bling_trace_device(bling_ctx* ctx, const void* rays_soa_dev, size_t n, int any_hit,
                        void* t_dev, void* prim_dev, void* bary_dev, int repeats, double* ms_out);
 
-/* Parity hook: radiance of individual camera samples, Path.li for sample n of extent pixel
- * (x, y) (Integrator/Path.hs:38-39 after Camera.fireRay).  samples: 3 ints (x, y, n) per sample;
+/* Parity hook: radiance of individual camera samples, the uploaded scene's surface integrator
+ * (Path.li, Integrator/Path.hs:38-39; DirectLighting; BidirPath's contrib, BidirPath.hs:50-96) for
+ * sample n of extent pixel (x, y) after Camera.fireRay.  samples: 3 ints (x, y, n) per sample;
  * L_out: 16 floats per sample (the spectrum before addSample's NaN filter); img_out: 2 floats per
- * sample (imageX, imageY), may be NULL.  Host buffers. */
+ * sample (imageX, imageY), may be NULL.  Host buffers.  stats (may be NULL) receives the ray counts;
+ * for the bidirectional integrator: rays_camera = camera samples traced, rays_continuation = the
+ * closest-hit queries of both subpaths' segments (the light ray included), rays_mis = estimateDirect's
+ * BSDF-MIS rays, rays_shadow = its shadow rays plus the connections' occluded queries,
+ * path_vertices = the vertices of both subpaths. */
 int bling_sample_li(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, const int32_t* samples, size_t n,
                     float* L_out, float* img_out, bling_stats* stats);
+
+/* Parity hook of the bidirectional integrator (BLING_INTEGRATOR_BIDIR scenes, else BLING_EINVAL): the
+ * terms of contrib (BidirPath.hs:70-96) for the same samples as bling_sample_li.  terms_out: 3 x 16
+ * floats per sample -- ld (the weighted direct terms), le, l (the connections; zero where a subpath is
+ * empty, the case in which contrib leaves it out); lens_out: 4 ints per sample -- eye subpath
+ * length, light subpath length, and the two masks whose bit i says that vertex i's sampled lobe was
+ * specular.  A parity mismatch so names its term. */
+int bling_debug_bidir_terms(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, const int32_t* samples, size_t n,
+                            float* terms_out, int32_t* lens_out);
 
 /* Debug hook (parity diagnosis): bling_sample_li plus one record of BLING_DV_FIELDS floats per path
  * vertex (vertex d of sample k at vtx_out[(k * BLING_DV_DEPTHS + d) * BLING_DV_FIELDS]; NaN where a

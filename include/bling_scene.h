@@ -244,7 +244,8 @@ enum bling_renderer_kind {
 /* the sampler renderer's surface integrator (IO/IntegratorParser.hs:15-47) */
 enum bling_integrator_kind {
     BLING_INTEGRATOR_PATH = 0,     /* path maxDepth sampleDepth        (Integrator/Path.hs)           */
-    BLING_INTEGRATOR_DIRECT = 1    /* directLighting maxDepth          (Integrator/DirectLighting.hs) */
+    BLING_INTEGRATOR_DIRECT = 1,   /* directLighting maxDepth          (Integrator/DirectLighting.hs) */
+    BLING_INTEGRATOR_BIDIR = 2     /* bidir maxDepth sampleDepth       (Integrator/BidirPath.hs)      */
 };
 
 typedef struct bling_render_config {
