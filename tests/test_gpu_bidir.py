@@ -15,6 +15,7 @@ from bling_amd import _ffi
 from bling_amd.render import BlingError, Context
 from bling_amd.scene import load_config
 from bd_ref import BidirRef, parity_samples, results as bd_results
+from film_ref import pass_samples as _pass_samples
 from parity_util import film_errors, report
 
 pytestmark = pytest.mark.gpu
@@ -105,23 +106,6 @@ def test_film_against_the_restatement(device):
     report("bidir_film", **e, rays_device=_rays(st), rays_ref=rst.rays())
     assert np.isfinite(film).all() and _rays(st) == rst.rays() and st.camera_samples == rst.samples
     assert e["rel_l2"] <= FILM_L2 and e["pix_max"] <= FILM_PIX, e
-
-
-def _pass_samples(job, sample_major, shard=(0, 1)):
-    """The (x, y, n) camera samples of a pass in its slot order: the shard's splitWindow tiles in order,
-    within a tile k_raygen's order (pixel-major: slot = pixel * spp + n; sample-major: n * pixels +
-    pixel; pixels row by row)."""
-    x0, x1, y0, y1 = job.extent()
-    spp, out, k = job.spp, [], 0
-    for ty in range(y0, y1 + 1, 16):
-        for tx in range(x0, x1 + 1, 16):
-            if k % shard[1] == shard[0]:
-                tw, th = min(tx + 15, x1) - tx + 1, min(ty + 15, y1) - ty + 1
-                j = np.arange(tw * th * spp)
-                pt, n = (j % (tw * th), j // (tw * th)) if sample_major else (j // spp, j % spp)
-                out.append(np.stack([tx + pt % tw, ty + pt // tw, n], 1))
-            k += 1
-    return np.concatenate(out).astype(np.int32)
 
 
 @pytest.mark.parametrize("shard", [(0, 1), (1, 2)])
