@@ -8,6 +8,7 @@
 #   bling_amd/_lib/libbling_mathcheck.so  exhaustive device check of common/fast_cr.h (tests)
 #   tests/ref/_build/liblt_ref.so     CPU restatement of the light tracer over the oracle (tests)
 #   tests/ref/_build/libbd_ref.so     CPU restatement of the bidirectional integrator over the oracle (tests)
+#   tests/ref/_build/libmlt_ref.so    CPU restatement of the Metropolis renderer over that one (tests)
 
 HIPCC    ?= /opt/rocm/bin/hipcc
 CXX      ?= g++
@@ -44,13 +45,15 @@ HIPFLAGS  := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -ffp-contract=off -fno-
              -Wno-unused-result -munsafe-fp-atomics
 
 all: $(LIBDIR)/libbling_host.so $(LIBDIR)/libbling_hip.so $(ORADIR)/liboracle.so $(LIBDIR)/bling \
-     $(LIBDIR)/libbling_mathcheck.so $(LTRDIR)/liblt_ref.so $(LTRDIR)/libbd_ref.so
+     $(LIBDIR)/libbling_mathcheck.so $(LTRDIR)/liblt_ref.so $(LTRDIR)/libbd_ref.so \
+     $(LTRDIR)/libmlt_ref.so
 
 host: $(LIBDIR)/libbling_host.so
 oracle: $(ORADIR)/liboracle.so
 core: $(LIBDIR)/libbling_hip.so
 ltref: $(LTRDIR)/liblt_ref.so
 bdref: $(LTRDIR)/libbd_ref.so
+mltref: $(LTRDIR)/libmlt_ref.so
 
 $(LIBDIR)/libbling_host.so: $(HOST_SRC) $(HOST_HDR)
 	@mkdir -p $(LIBDIR)
@@ -70,6 +73,11 @@ $(LTRDIR)/libbd_ref.so: tests/ref/bidir_ref.cpp $(ORA_SRC) $(ORA_HDR)
 	@mkdir -p $(LTRDIR)
 	$(CXX) $(HOSTFLAGS) -Wno-subobject-linkage -fopenmp -shared -o $@ tests/ref/bidir_ref.cpp
 
+# the Metropolis renderer's restatement includes the bidirectional one; tests only
+$(LTRDIR)/libmlt_ref.so: tests/ref/mlt_ref.cpp tests/ref/bidir_ref.cpp $(ORA_SRC) $(ORA_HDR) bling_amd/csrc/common/sky_model.h
+	@mkdir -p $(LTRDIR)
+	$(CXX) $(HOSTFLAGS) -Wno-subobject-linkage -fopenmp -shared -o $@ tests/ref/mlt_ref.cpp
+
 # one object per unit (core, sppm driver, one per kernel feature profile) so make -j compiles the
 # kernel instantiations in parallel
 $(OBJDIR)/%.o: bling_amd/csrc/core/% $(CORE_HDR)
@@ -78,6 +86,8 @@ $(OBJDIR)/%.o: bling_amd/csrc/core/% $(CORE_HDR)
 
 # the all-features bidir units include the driver unit's source
 $(OBJDIR)/bidir_pass_walk.hip.o $(OBJDIR)/bidir_pass_connect.hip.o: bling_amd/csrc/core/bidir_pass.hip
+# and so does the Metropolis walk unit
+$(OBJDIR)/mlt_pass_walk.hip.o: bling_amd/csrc/core/mlt_pass.hip
 
 $(LIBDIR)/libbling_hip.so: $(CORE_OBJ)
 	@mkdir -p $(LIBDIR)
@@ -102,4 +112,4 @@ variant: $(CORE_OBJ)
 clean:
 	rm -rf $(LIBDIR) $(ORADIR) $(LTRDIR) build
 
-.PHONY: all host oracle core ltref bdref clean variant
+.PHONY: all host oracle core ltref bdref mltref clean variant

@@ -84,6 +84,29 @@ class LightTracer(C.Structure):
     _fields_ = [("pass_photons", C.c_int32), ("pixel_area", C.c_float), ("w2r", C.c_float * 16)]
 
 
+class Metropolis(C.Structure):
+    """bling_metropolis (include/bling_scene.h): appended to bling_scene_desc after the light tracer block."""
+    _fields_ = [("max_depth", C.c_int32), ("mpp", C.c_float), ("bootstrap", C.c_int32), ("plarge", C.c_float),
+                ("chains", C.c_int32)]
+
+
+class MltStats(C.Structure):
+    """bling_mlt_stats (include/bling.h)."""
+    _fields_ = [("b", C.c_double), ("mutations", C.c_uint64), ("large_steps", C.c_uint64), ("accepted", C.c_uint64),
+                ("splats", C.c_uint64), ("dropped", C.c_uint64), ("rays_camera", C.c_uint64),
+                ("rays_continuation", C.c_uint64), ("rays_mis", C.c_uint64), ("rays_shadow", C.c_uint64),
+                ("path_vertices", C.c_uint64), ("ms_total", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class MltRecord(C.Structure):
+    """bling_mlt_record (include/bling.h): one (chain, mutation) of the Metropolis renderer's record mode, 32 bytes."""
+    _fields_ = [("chain", C.c_uint32), ("mutation", C.c_uint32), ("x", C.c_float), ("y", C.c_float),
+                ("i_prop", C.c_float), ("a", C.c_float), ("flags", C.c_uint32), ("pad", C.c_uint32)]
+
+
 class RenderConfig(C.Structure):
     _fields_ = [("renderer", C.c_int32), ("sampler", C.c_int32), ("nu", C.c_int32), ("nv", C.c_int32),
                 ("spp", C.c_int32), ("max_depth", C.c_int32), ("sample_depth", C.c_int32),
@@ -115,6 +138,7 @@ def host() -> C.CDLL:
         lib.bling_host_film_to_rgb.argtypes = [c_f32p, C.c_int, C.c_int, c_f32p]
         lib.bling_host_film_splat_to_rgb.argtypes = [c_f32p, c_f32p, C.c_float, C.c_int, C.c_int, c_f32p]
         lib.bling_host_light.argtypes = [C.c_void_p, C.POINTER(LightTracer)]
+        lib.bling_host_metropolis.argtypes = [C.c_void_p, C.POINTER(Metropolis)]
         lib.bling_host_write_hdr.argtypes = [C.c_char_p, c_f32p, C.c_int, C.c_int]
         lib.bling_host_write_hdr.restype = C.c_int
         lib.bling_host_rgb_pixels.argtypes = [c_f32p, C.c_int, C.c_int, C.POINTER(C.c_uint8)]
@@ -128,7 +152,7 @@ HIP_SYMBOLS = ["bling_create", "bling_scene_upload", "bling_scene_validate", "bl
                "bling_trace", "bling_trace_device", "bling_sample_li", "bling_sample_li_vertices", "bling_pass_tile_layout",
                "bling_film_add_tiles", "bling_film_add_shards", "bling_sppm_pass", "bling_sppm_pixel_stats", "bling_sppm_reset",
                "bling_render", "bling_debug_stream_bytes", "bling_debug_scene_info", "bling_debug_mis_culled", "bling_debug_set_mis_cull", "bling_debug_set_pipeline", "bling_debug_pass_results", "bling_debug_compact", "bling_debug_sppm_hitpoints", "bling_debug_sppm_buckets",
-               "bling_light_pass", "bling_debug_light_records", "bling_debug_bidir_terms", "bling_destroy", "bling_last_error", "bling_version"]
+               "bling_light_pass", "bling_debug_light_records", "bling_mlt_pass", "bling_debug_mlt_records", "bling_debug_mlt_boot", "bling_debug_mlt_set_boot", "bling_debug_bidir_terms", "bling_destroy", "bling_last_error", "bling_version"]
 
 
 class Progress(C.Structure):
@@ -197,6 +221,16 @@ def hip() -> C.CDLL:
         lib.bling_debug_light_records.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                   C.POINTER(LightRecord), C.c_size_t, C.POINTER(C.c_size_t)]
         lib.bling_debug_light_records.restype = C.c_int
+        if hasattr(lib, "bling_mlt_pass"):            # older experiment builds lack the Metropolis renderer
+            lib.bling_mlt_pass.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, c_f32p, C.POINTER(MltStats)]
+            lib.bling_mlt_pass.restype = C.c_int
+            lib.bling_debug_mlt_records.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                    C.POINTER(MltRecord), C.c_size_t, C.POINTER(C.c_size_t), c_u32p, c_f32p]
+            lib.bling_debug_mlt_records.restype = C.c_int
+            lib.bling_debug_mlt_boot.argtypes = [c_f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, c_f32p, c_u32p]
+            lib.bling_debug_mlt_boot.restype = C.c_int
+            lib.bling_debug_mlt_set_boot.argtypes = [C.c_void_p, c_f32p, C.c_uint32]
+            lib.bling_debug_mlt_set_boot.restype = C.c_int
         if hasattr(lib, "bling_debug_bidir_terms"):   # older experiment builds lack it
             lib.bling_debug_bidir_terms.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.c_size_t,
                                                     c_f32p, C.POINTER(C.c_int32)]

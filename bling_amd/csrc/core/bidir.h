@@ -69,8 +69,8 @@ struct BdRays { unsigned long long cam, cont, mis, shadow, verts, dropped; };
 // sampleOneLight (Scene.hs:61-118) of an eye vertex with estimateDirect's dimensions (:144-147): the
 // light sample and its any-hit shadow ray, the BSDF-MIS sample and its closest-hit ray, the power
 // heuristic -- the oracle's order, resolve_L's operations (wavefront.h).
-template <uint32_t F>
-DEV Sp bd_direct(const DevScene& S, const LdsScene& L, const SampleKey& k, const Bsdf& bsdf, V3 wo, float eps, int i,
+template <uint32_t F, class K = SampleKey>
+DEV Sp bd_direct(const DevScene& S, const LdsScene& L, const K& k, const Bsdf& bsdf, V3 wo, float eps, int i,
                  BdRays& R) {
   const int lc = S.num_lights;
   Sp ld = sconst(0.f);
@@ -132,8 +132,10 @@ DEV Sp bd_direct(const DevScene& S, const LdsScene& L, const SampleKey& k, const
 // first clause matches the intersection before the depth guard, so the segment after vertex md - 1 is
 // traced too (trap T31); a vertex whose sample is black or has pdf 0 is kept and ends its walk.  The
 // roulette draws are compared against rrProb = 1 and not drawn.
-template <uint32_t F>
-DEV void bd_walks(const DevScene& S, const LdsScene& L, const BdBufs& B, uint32_t sid, const SampleKey& k,
+// K is the sample source: rnd1(S, k, dim) / rnd2(S, k, dim, &a, &b) give the sample's values -- the
+// counter sampler's SampleKey (dev_shade.h), or the Metropolis renderer's primary sample (mlt.h PssKey).
+template <uint32_t F, class K = SampleKey>
+DEV void bd_walks(const DevScene& S, const LdsScene& L, const BdBufs& B, uint32_t sid, const K& k,
                   const Ray& lray, V3 lwi, const Sp& lalpha, const Ray& cam, int& ne, int& nl, uint32_t& emask,
                   uint32_t& lmask, Sp& le, BdRays& R) {
   const int md = B.md;
@@ -179,7 +181,7 @@ DEV void bd_walks(const DevScene& S, const LdsScene& L, const BdBufs& B, uint32_
           le = le + alpha * e;
         }
         prev_spec = spec;
-        const Sp d = bd_direct<F>(S, L, k, bsdf, wi, eps, depth, R) * alpha;   // estimateDirect (:142-154)
+        const Sp d = bd_direct<F, K>(S, L, k, bsdf, wi, eps, depth, R) * alpha;   // estimateDirect (:142-154)
         bd_store_sp(B.ld, bd_at(B, depth, sid), d);
       }
       ++depth; ++R.verts;
@@ -213,6 +215,28 @@ DEV void bd_flush(Counters* C, const BdRays& R) {
     if (v) atomicAdd(&C->vertices, v);
     if (d) atomicAdd(&C->dropped, d);
   }
+}
+
+// lightPath's first segment (:167-173): sampleLightRay (Scene.hs:121-135) of the sample's one light
+template <uint32_t F, class K = SampleKey>
+DEV void bd_light_start(const DevScene& S, const K& k, Ray& lray, V3& lwi, Sp& lalpha) {
+  const float ul = rnd1(S, k, 0);
+  float uo1, uo2, ud1, ud2;
+  rnd2(S, k, 0, &uo1, &uo2);
+  rnd2(S, k, 1, &ud1, &ud2);
+  float pdf = 0.f;
+  Sp li = sconst(0.f);
+  Ray ray{mk(0.f, 0.f, 0.f), mk(0.f, 1.f, 0.f), 0.f, 0.f};
+  V3 nl3 = mk(0.f, 1.f, 0.f);
+  if (S.num_lights > 0) {
+    const int lc = S.num_lights;
+    const int ln = lc == 1 ? 0 : min((int)floorf(ul * (float)lc), lc - 1);
+    pdf = light_ray<F>(S, gen(S.lights[ln]), uo1, uo2, ud1, ud2, li, ray, nl3);
+    if (lc > 1) pdf = pdf / (float)lc;
+  }
+  const V3 wo = -ray.d;                                              // not normalised, pdf not tested (trap T25)
+  li = sscale(li, fabsf(dot(nl3, wo)) / pdf);
+  lray = ray; lwi = wo; lalpha = li;
 }
 
 // The camera samples of a wave: tile mode (tiles != nullptr: grid (blocks, tile), k_raygen's sample
@@ -262,25 +286,7 @@ static __global__ __launch_bounds__(256) void k_bd_walk(const DevScene* __restri
     Sp le = sconst(0.f), lalpha;
     Ray lray;
     V3 lwi;
-    {                                                                // lightPath (:167-173)
-      const float ul = rnd1(S, k, 0);
-      float uo1, uo2, ud1, ud2;
-      rnd2(S, k, 0, &uo1, &uo2);
-      rnd2(S, k, 1, &ud1, &ud2);
-      float pdf = 0.f;                                               // sampleLightRay (Scene.hs:121-135)
-      Sp li = sconst(0.f);
-      Ray ray{mk(0.f, 0.f, 0.f), mk(0.f, 1.f, 0.f), 0.f, 0.f};
-      V3 nl3 = mk(0.f, 1.f, 0.f);
-      if (S.num_lights > 0) {
-        const int lc = S.num_lights;
-        const int ln = lc == 1 ? 0 : min((int)floorf(ul * (float)lc), lc - 1);
-        pdf = light_ray<F>(S, gen(S.lights[ln]), uo1, uo2, ud1, ud2, li, ray, nl3);
-        if (lc > 1) pdf = pdf / (float)lc;
-      }
-      const V3 wo = -ray.d;                                          // not normalised, pdf not tested (trap T25)
-      li = sscale(li, fabsf(dot(nl3, wo)) / pdf);
-      lray = ray; lwi = wo; lalpha = li;
-    }
+    bd_light_start<F>(S, k, lray, lwi, lalpha);
     bd_walks<F>(S, L, B, sid, k, lray, lwi, lalpha, cam, ne, nl, emask, lmask, le, R);
     bd_store_sp(B.le, sid, le);
     B.info[sid] = make_uint4((uint32_t)ne, (uint32_t)nl, emask, lmask);

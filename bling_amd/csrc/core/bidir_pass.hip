@@ -32,9 +32,7 @@ template void bidir_connect_launch<FT_ALL>(bling_ctx*, const BdBufs&, uint32_t);
 extern template void bidir_walk_launch<FT_ALL>(BLING_BD_WALK_ARGS);
 extern template void bidir_connect_launch<FT_ALL>(bling_ctx*, const BdBufs&, uint32_t);
 
-int bidir_wave(bling_ctx* c, const WaveState& W, const TileDesc* tiles, unsigned n_tiles, uint32_t max_tile,
-               const int32_t* list, uint32_t n, uint32_t seed, uint32_t pass, float* terms) {
-  if (n == 0) return 0;
+BdBufs bidir_bufs(bling_ctx* c, uint32_t n, float* terms) {
   BidirState& P = c->bidir;
   if (P.md != c->S.max_depth || P.md < 1 || P.md > BD_MAX_DEPTH || n > P.cap)
     throw std::runtime_error("bidir vertex buffers do not fit the wave");
@@ -43,15 +41,23 @@ int bidir_wave(bling_ctx* c, const WaveState& W, const TileDesc* tiles, unsigned
   B.ld = P.ld.p; B.conn = P.conn.p; B.le = P.le.p; B.info = P.info.p;
   B.terms = reinterpret_cast<float4*>(terms);
   B.cap = P.cap; B.md = P.md;
-  if ((c->features & ~kProfiles[0]) == 0u) {
-    bidir_walk_launch<kProfiles[0]>(c, W, B, tiles, n_tiles, max_tile, list, n, seed, pass);
-    bidir_connect_launch<kProfiles[0]>(c, B, n);
-  } else {
-    bidir_walk_launch<FT_ALL>(c, W, B, tiles, n_tiles, max_tile, list, n, seed, pass);
-    bidir_connect_launch<FT_ALL>(c, B, n);
-  }
+  return B;
+}
+
+void bidir_connect_finish(bling_ctx* c, const WaveState& W, const BdBufs& B, uint32_t n) {
+  if ((c->features & ~kProfiles[0]) == 0u) bidir_connect_launch<kProfiles[0]>(c, B, n);
+  else bidir_connect_launch<FT_ALL>(c, B, n);
   k_bd_finish<<<(n + 255) / 256, 256, 0, c->stream>>>(W, B, n, c->counters.p);
   HIPCHK(hipGetLastError());
+}
+
+int bidir_wave(bling_ctx* c, const WaveState& W, const TileDesc* tiles, unsigned n_tiles, uint32_t max_tile,
+               const int32_t* list, uint32_t n, uint32_t seed, uint32_t pass, float* terms) {
+  if (n == 0) return 0;
+  const BdBufs B = bidir_bufs(c, n, terms);
+  if ((c->features & ~kProfiles[0]) == 0u) bidir_walk_launch<kProfiles[0]>(c, W, B, tiles, n_tiles, max_tile, list, n, seed, pass);
+  else bidir_walk_launch<FT_ALL>(c, W, B, tiles, n_tiles, max_tile, list, n, seed, pass);
+  bidir_connect_finish(c, W, B, n);
   return 3;
 }
 #endif

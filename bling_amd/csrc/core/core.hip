@@ -98,6 +98,17 @@ void validate_scene(const bling_scene_desc* d) {
     if (d->config.sppm_photons < 1 || d->config.sppm_threads < 1) throw std::invalid_argument("bad sppm photon count");
   } else if (d->config.renderer == BLING_RENDERER_LIGHT) {
     if (d->light.pass_photons < 1) throw std::invalid_argument("light tracer passPhotons < 1");
+  } else if (d->config.renderer == BLING_RENDERER_METROPOLIS) {
+    const bling_metropolis& m = d->metropolis;
+    // the chain's integrator is the bidirectional one with maxDepth = sampleDepth (Metropolis.hs:46-49)
+    if (m.max_depth < 1 || m.max_depth > BD_MAX_DEPTH)
+      throw std::invalid_argument("metropolis maxDepth outside [1, " + std::to_string(BD_MAX_DEPTH) + "]");
+    if (m.bootstrap < 1) throw std::invalid_argument("metropolis bootstrap < 1");
+    const float mut = mlt_mutations(m, d->config.width, d->config.height);
+    if (!(mut >= 1.f)) throw std::invalid_argument("metropolis mpp gives no mutation (floor (mpp * nPixels) < 1)");
+    if (!(mut < 2147483648.f)) throw std::invalid_argument("metropolis mpp gives 2^31 mutations or more");
+    if (m.chains < 1) throw std::invalid_argument("metropolis chains < 1");
+    if ((uint32_t)m.chains > MLT_MAX_CHAINS) throw std::invalid_argument("metropolis chains > 2^20");
   } else if (d->config.spp <= 0) {
     throw std::invalid_argument("bad render config");
   } else if (d->config.integrator == BLING_INTEGRATOR_DIRECT) {
@@ -461,8 +472,12 @@ void upload_scene(bling_ctx* c, const bling_scene_desc* d) {
   S.sampler = cfg.sampler; S.nu = cfg.nu; S.nv = cfg.nv; S.spp = cfg.spp;
   S.max_depth = cfg.max_depth; S.sample_depth = cfg.sample_depth;
   S.integrator = cfg.integrator;
+  if (cfg.renderer == BLING_RENDERER_METROPOLIS) {                   // mkBidirPathIntegrator md md (Metropolis.hs:46-49)
+    S.integrator = BLING_INTEGRATOR_BIDIR;
+    S.max_depth = S.sample_depth = d->metropolis.max_depth;
+  }
   if (S.integrator == BLING_INTEGRATOR_DIRECT) S.n1d = S.n2d = 2 * cfg.max_depth;   // DirectLighting.hs:17-18
-  else if (S.integrator == BLING_INTEGRATOR_BIDIR) { S.n1d = 12 * cfg.sample_depth + 1; S.n2d = 9 * cfg.sample_depth + 2; }   // BidirPath.hs:44-48
+  else if (S.integrator == BLING_INTEGRATOR_BIDIR) { S.n1d = 12 * S.sample_depth + 1; S.n2d = 9 * S.sample_depth + 2; }   // BidirPath.hs:44-48
   else { S.n1d = 4 * cfg.sample_depth; S.n2d = 3 * cfg.sample_depth; }              // Path.hs:26-28
   if (cfg.spp > (1 << 24)) throw std::runtime_error("more than 2^24 samples per pixel (the sampler's permutation, counter_rng.h)");
   S.fd_spp = FastDiv::make((uint32_t)std::max(1, cfg.spp));
@@ -486,8 +501,11 @@ void upload_scene(bling_ctx* c, const bling_scene_desc* d) {
   c->film_dev.free();
   c->cfg = cfg;
   c->lt = d->light;
+  c->mp = d->metropolis;
   c->sppm.free_all();
   c->light.free_all();
+  c->mlt.free_all();
+  c->mlt_boot_override.clear();
 }
 
 // A pass whose paths fit one wave runs as two half-waves on two streams (core_wave.h run_wave_pair_t)
@@ -1551,6 +1569,76 @@ int bling_debug_light_records(bling_ctx* c, uint32_t seed, uint32_t pass_index, 
     std::sort(records, records + got, [](const bling_light_record& a, const bling_light_record& b) {
       return a.photon != b.photon ? a.photon < b.photon : a.depth < b.depth;
     });
+    return BLING_OK;
+  });
+}
+
+// ---- Metropolis renderer (mlt.h, mlt_pass.hip)
+static int mlt_ready(bling_ctx* c) {
+  if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
+  if (c->cfg.renderer != BLING_RENDERER_METROPOLIS) throw std::invalid_argument("the uploaded scene's renderer is not metropolis");
+  if (!c->peers.empty()) throw std::invalid_argument("the Metropolis renderer runs on a single-device context");
+  return BLING_OK;
+}
+
+int bling_mlt_pass(bling_ctx* c, uint32_t seed, uint32_t pass_index, float* splat_inout, bling_mlt_stats* st) {
+  return guarded([&] {
+    if (!c) throw std::invalid_argument("null argument");
+    if (int rc = mlt_ready(c)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    LightState& P = c->light;
+    const size_t ns = (size_t)c->S.width * c->S.height * 3;
+    if (P.splat.n != ns) P.splat.alloc(ns);
+    if (splat_inout) HIPCHK(hipMemcpy(P.splat.p, splat_inout, ns * sizeof(float), hipMemcpyHostToDevice));
+    else HIPCHK(hipMemset(P.splat.p, 0, ns * sizeof(float)));
+    if (st) std::memset(st, 0, sizeof *st);
+    mlt_pass_run(c, seed, pass_index, true, 0u, 0u, st, nullptr);
+    if (splat_inout) HIPCHK(hipMemcpy(splat_inout, P.splat.p, ns * sizeof(float), hipMemcpyDeviceToHost));
+    return BLING_OK;
+  });
+}
+
+int bling_debug_mlt_records(bling_ctx* c, uint32_t seed, uint32_t pass_index, uint32_t first_chain, uint32_t n_chains,
+                            bling_mlt_record* records, size_t cap, size_t* n, uint32_t* starts, float* b) {
+  return guarded([&] {
+    if (!c || !n || (cap && !records)) throw std::invalid_argument("null argument");
+    *n = 0;
+    if (int rc = mlt_ready(c)) return rc;
+    const uint64_t C = (uint64_t)c->mp.chains;
+    if ((uint64_t)first_chain + n_chains > C) throw std::invalid_argument("chain range beyond chains");
+    if (n_chains == 0) return BLING_OK;
+    const uint64_t M = (uint64_t)mlt_mutations(c->mp, c->S.width, c->S.height);
+    uint64_t need = 0;
+    for (uint64_t k = first_chain; k < (uint64_t)first_chain + n_chains; ++k) need += M / C + (k < M % C ? 1 : 0);
+    *n = (size_t)need;
+    if (need > cap) {
+      g_err = "mlt records: " + std::to_string(need) + " records exceed the capacity " + std::to_string(cap);
+      return BLING_EINVAL;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    MltOut out;
+    mlt_pass_run(c, seed, pass_index, false, first_chain, n_chains, nullptr, &out);
+    if (out.rec.size() != need) throw std::runtime_error("mlt records: count mismatch");
+    if (need) std::memcpy(records, out.rec.data(), need * sizeof(bling_mlt_record));
+    if (starts) std::memcpy(starts, out.start.data() + first_chain, (size_t)n_chains * sizeof(uint32_t));
+    if (b) *b = out.b;
+    return BLING_OK;
+  });
+}
+
+int bling_debug_mlt_boot(const float* I, uint32_t n, uint32_t seed, uint32_t pass_index, uint32_t chains, float* b,
+                         uint32_t* starts) {
+  return guarded([&] {
+    if (!I || !b || !starts || n < 1 || chains < 1) throw std::invalid_argument("null argument");
+    *b = mlt_boot_select(I, n, seed, pass_index, chains, starts);
+    return BLING_OK;
+  });
+}
+
+int bling_debug_mlt_set_boot(bling_ctx* c, const float* I, uint32_t n) {
+  return guarded([&] {
+    if (!c || (n && !I)) throw std::invalid_argument("null argument");
+    c->mlt_boot_override.assign(I, I + n);
     return BLING_OK;
   });
 }

@@ -21,6 +21,7 @@
 #include "sppm.h"
 #include "light_tracer.h"
 #include "bidir.h"
+#include "mlt.h"
 
 namespace bcore {
 using namespace bd;
@@ -125,6 +126,20 @@ struct LightState {
   void free_all() { splat.free(); ctr.free(); rec.free(); rec_count.free(); }
 };
 
+// Metropolis renderer state (mlt.h): the chains' primary samples, their current contribution, the
+// bootstrap contributions and the record buffer of record mode; the splat image is the light tracer's
+struct MltState {
+  DBuf<float> cur, prop, cur_l, boot_i;
+  DBuf<float4> lfull;
+  DBuf<uint32_t> flags, start;
+  DBuf<unsigned long long> ctr;
+  DBuf<uint4> rec;
+  void free_all() {
+    for (auto* b : {&cur, &prop, &cur_l, &boot_i}) b->free();
+    lfull.free(); flags.free(); start.free(); ctr.free(); rec.free();
+  }
+};
+
 }  // namespace bcore
 
 // the context lives in the global namespace (include/bling.h declares `struct bling_ctx`)
@@ -224,6 +239,9 @@ struct bling_ctx {
   LightState light;
   BidirState bidir;
   bling_light_tracer lt{};      // the uploaded scene's light tracer block (photons per pass)
+  MltState mlt;
+  bling_metropolis mp{};        // the uploaded scene's Metropolis block
+  std::vector<float> mlt_boot_override;   // bling_debug_mlt_set_boot: I values that replace the evaluated ones
   // Multi-device fan-out (bling_create with n_devices > 1): one context per further device; every
   // device renders its share as tile images, the peers push theirs over xGMI into stage, and the
   // primary adds them all (Rendering.hs:118).
@@ -389,6 +407,30 @@ inline uint32_t profile_of(uint32_t need) {
   with_profile(need, [&](auto prof) { p = decltype(prof)::value; });
   return p;
 }
+
+// The launches bidir_wave is made of, for the Metropolis driver (mlt_pass.hip): the vertex buffers of a
+// wave of n samples, and connect + finish of a walked wave.
+BdBufs bidir_bufs(bling_ctx* c, uint32_t n, float* terms);
+void bidir_connect_finish(bling_ctx* c, const WaveState& W, const BdBufs& B, uint32_t n);
+// What a Metropolis pass returns beside the splat image (mlt_pass.hip): b', the chains' start samples
+// (bootstrap sample indices) and, in record mode, the records sorted by (chain, mutation).
+struct MltOut {
+  float b = 0.f;
+  std::vector<uint32_t> start;
+  std::vector<bling_mlt_record> rec;
+};
+// One pass of the Metropolis renderer; splat: into the context's light.splat image; records of chains
+// rec_first .. rec_first + rec_chains - 1 (0 = off).  Throws std::invalid_argument where the reference
+// would stop with an error (bootstrap selection on an unwritten slot).
+void mlt_pass_run(bling_ctx* c, uint32_t seed, uint32_t pass, bool splat, uint32_t rec_first, uint32_t rec_chains,
+                  bling_mlt_stats* st, MltOut* out);
+// The host bookkeeping of bootstrap (mlt_pass.hip): b' and the chains' start samples from the I values.
+float mlt_boot_select(const float* I, uint32_t nboot, uint32_t seed, uint32_t pass, uint32_t chains, uint32_t* start);
+// Bootstrap samples evaluated per wave when there are more of them than chains; it bounds the vertex
+// buffers a large `bootstrap` asks for (bd_sample_bytes per sample: 100 MB at maxDepth 16)
+constexpr uint32_t kMltBootChunk = 16384u;
+// M = floor (mpp * nPixels) (Metropolis.hs:86) as a float; NaN or < 1 is refused by validation
+inline float mlt_mutations(const bling_metropolis& m, int w, int h) { return floorf(m.mpp * (float)(w * h)); }
 
 }  // namespace bcore
 

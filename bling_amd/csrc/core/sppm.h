@@ -23,6 +23,10 @@ constexpr uint32_t DIM_SPPM_1D = 0x100000u, DIM_SPPM_2D = 0x200000u, SPPM_PHOTON
 // sample_key(pk, i & 0xFFFF) -- a pixel tag neither a camera pixel (< 2^30) nor SPPM_PHOTON_PIXEL | k
 // reaches -- and only fresh dimensions: 1D DIM_FRESH1D + dim with ul = 0 and at vertex d ubc = 1 + 2 d,
 // roulette = 2 + 2 d; 2D DIM_FRESH2D + 2 dim (+ 1) with ulo = 0, uld = 1 and at vertex d ubd = 2 + d.
+// Metropolis renderer (mlt.h): chain c draws from pixel tag MLT_CHAIN_PIXEL | c = 0x50000000 | c (c < 2^20),
+// sample = the mutation index (MLT_START_SAMPLE for the start selection); bootstrap sample i from pixel tag
+// MLT_BOOT_PIXEL = 0x60000000, sample = i; dimension DIM_FRESH1D + the draw's ordinal.  Neither tag is a
+// camera pixel, LT_PIXEL | i >> 16 (i >> 16 < 2^16) or SPPM_PHOTON_PIXEL | k.
 constexpr uint32_t LT_PIXEL = 0x40000000u;
 constexpr uint32_t LT_DIM_UL = 0u, LT_DIM_UBC = 1u, LT_DIM_ROULETTE = 2u;      // 1D
 constexpr uint32_t LT_DIM_ULO = 0u, LT_DIM_ULD = 1u, LT_DIM_UBD = 2u;          // 2D

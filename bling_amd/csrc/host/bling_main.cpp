@@ -63,6 +63,34 @@ int main(int argc, char** argv) {
     bling_host_free(hs);
     return 0;
   }
+  if (d->config.renderer == BLING_RENDERER_METROPOLIS) {
+    // instance Renderer Metropolis (Renderer/Metropolis.hs:76-120): the film stays empty, every pass adds
+    // its splats, and the image of pass p weighs them with bnext / p, bnext = lerp (1 / p) b b' from b = 1
+    std::vector<float> splat((size_t)w * h * 3, 0.f);
+    float b = 1.f;
+    for (int p = 1; p <= passes; ++p) {
+      bling_mlt_stats st;
+      if (bling_mlt_pass(ctx, 0x0B11A6u, (uint32_t)p, splat.data(), &st) != 0) { std::fprintf(stderr, "%s\n", bling_last_error()); return 1; }
+      const float t = 1.f / (float)p;
+      b = (1.f - t) * b + t * (float)st.b;
+      std::printf("pass %d: %.1f ms, %llu mutations (%llu large, %llu accepted), b = %g, %.2f Mmutations/s\n", p, st.ms_total,
+                  (unsigned long long)st.mutations, (unsigned long long)st.large_steps, (unsigned long long)st.accepted, b,
+                  st.mutations / (st.ms_total * 1e3));
+      const float sw = b / (float)p;
+      char name[512];
+      std::snprintf(name, sizeof name, "%s-%05d", out, p);
+      std::printf("Writing %s...\n", name);
+      bling_host_film_splat_to_rgb(film.data(), splat.data(), sw, w, h, rgb.data());
+      if (bling_host_write_png_splat((std::string(name) + ".png").c_str(), film.data(), splat.data(), sw, w, h) != 0 ||
+          bling_host_write_hdr((std::string(name) + ".hdr").c_str(), rgb.data(), w, h) != 0) {
+        std::fprintf(stderr, "%s\n", bling_host_last_error());
+        return 1;
+      }
+    }
+    bling_destroy(ctx);
+    bling_host_free(hs);
+    return 0;
+  }
   for (int p = 1; p <= passes; ++p) {
     bling_pass_params pp{0x0B11A6u, (uint32_t)p, 0, 1, 1, 0};
     bling_stats st;

@@ -271,6 +271,7 @@ struct Overrides {
   bool sppm = false; int sp_photons = 0, sp_md = 0; float sp_radius = 0.f, sp_alpha = 0.8f;
   int sppm_threads = 0;
   bool light = false; int lt_photons = 0;
+  bool mlt = false; int ml_md = 0, ml_boot = 0, ml_chains = INT32_MIN; float ml_mpp = 0.f, ml_plarge = 0.f;
 };
 
 struct Mat { bling_material m; };
@@ -288,6 +289,7 @@ struct Builder {
   bling_filter filter{};
   bling_camera camera{};
   bling_light_tracer lt{};
+  bling_metropolis mlt{};
   Xf xf = identityX();
   int material = 0;
   bool has_emit = false;
@@ -1195,9 +1197,16 @@ struct Parser {
       } else if (t == "light") {                      // RendererParser.hs:28-30: passPhotons comes first
         B.lt.pass_photons = named_int("passPhotons");
         B.cfg.renderer = BLING_RENDERER_LIGHT;
+      } else if (t == "metropolis") {                 // RendererParser.hs:32-38
+        B.mlt.max_depth = named_int("maxDepth");
+        B.mlt.mpp = named_float("mpp");
+        B.mlt.bootstrap = named_int("bootstrap");
+        B.mlt.plarge = named_float("plarge");
+        // directSamples > 0 selects mkNoDirectBidirIntegrator, whose eye path is `undefined`
+        // (BidirPath.hs:65-67): such a block cannot render in the reference and is not served
+        B.cfg.renderer = named_int("directSamples") > 0 ? BLING_RENDERER_OTHER : BLING_RENDERER_METROPOLIS;
       } else {
-        // metropolis: not served (trap T1); skip its arguments
-        B.cfg.renderer = BLING_RENDERER_OTHER;
+        B.cfg.renderer = BLING_RENDERER_OTHER;        // unknown to the reference's parser too: skip its arguments
         while (L.peekc() != '}') { if (L.peek_number()) L.flt(); else L.word(); }
       }
     });
@@ -1286,6 +1295,11 @@ Overrides parse_overrides(const char* s) {
       o.sp_alpha = parts.size() > 3 ? Fv(3) : 0.8f;
     }
     else if (k == "light") { o.light = true; o.lt_photons = I(0); }      // light=passPhotons
+    else if (k == "metropolis") {                       // metropolis=maxDepth,mpp,bootstrap,plarge[,chains]
+      o.mlt = true; o.ml_md = I(0); o.ml_mpp = Fv(1); o.ml_boot = I(2); o.ml_plarge = Fv(3);
+      if (parts.size() > 4) o.ml_chains = I(4);
+    }
+    else if (k == "chains") { o.ml_chains = I(0); }     // the Metropolis renderer's chains
     else if (k == "sppm_threads") { o.sppm_threads = I(0); if (o.sppm_threads < 1) throw ParseError("bad override " + kv); }
     else if (k == "filter") {
       o.filter = true;
@@ -1342,6 +1356,19 @@ int bling_host_load(const char* path, const char* overrides, bling_host_scene** 
       B.cfg.sppm_radius = B.ov.sp_radius; B.cfg.sppm_alpha = B.ov.sp_alpha;
     }
     if (B.ov.light) { B.cfg.renderer = BLING_RENDERER_LIGHT; B.lt.pass_photons = B.ov.lt_photons; }
+    if (B.ov.mlt) {
+      B.cfg.renderer = BLING_RENDERER_METROPOLIS;
+      B.mlt.max_depth = B.ov.ml_md; B.mlt.mpp = B.ov.ml_mpp; B.mlt.bootstrap = B.ov.ml_boot; B.mlt.plarge = B.ov.ml_plarge;
+    }
+    if (B.cfg.renderer == BLING_RENDERER_METROPOLIS) {
+      // the chain's integrator is mkBidirPathIntegrator md md (Metropolis.hs:46-49)
+      B.cfg.integrator = BLING_INTEGRATOR_BIDIR;
+      B.cfg.max_depth = B.cfg.sample_depth = B.mlt.max_depth;
+      // chains: 4096 unless overridden, at most one per mutation (M = floor (mpp * nPixels), :86)
+      const float m = std::floor(B.mlt.mpp * (float)(B.resX * B.resY));
+      B.mlt.chains = B.ov.ml_chains != INT32_MIN ? B.ov.ml_chains : 4096;
+      if (B.ov.ml_chains == INT32_MIN && m >= 1.f && m < (float)B.mlt.chains) B.mlt.chains = (int)m;
+    }
     // numCapabilities of the modelled reference run (SPPM.hs:449, 474): photons per pass are
     // threads * sn^2; 8 = this build machine's core count unless overridden
     B.cfg.sppm_threads = B.ov.sppm_threads > 0 ? B.ov.sppm_threads : 8;
@@ -1401,6 +1428,7 @@ int bling_host_load(const char* path, const char* overrides, bling_host_scene** 
     d.num_images = (uint32_t)B.images.size();
     d.images = B.images.data();
     d.light = B.lt;
+    d.metropolis = B.mlt;
     // the infinite lights' Dist2D arrays live in the parsed LightRec objects
     for (size_t k = 0; k < B.lights.size(); ++k) {
       if (B.lights[k].kind != BLING_LIGHT_INFINITE) continue;
@@ -1411,7 +1439,7 @@ int bling_host_load(const char* path, const char* overrides, bling_host_scene** 
     sm << "image " << B.resX << "x" << B.resY << ", prims " << d.num_prims << " (triangles "
        << d.num_triangles << ", shapes " << d.num_shapes << ", fractal " << d.fractal.present << "), lights "
        << d.num_lights << ", materials " << d.num_materials << ", renderer "
-       << (B.cfg.renderer == BLING_RENDERER_LIGHT ? "light" : B.cfg.renderer != BLING_RENDERER_SAMPLER_PATH ? "other" : B.cfg.integrator == BLING_INTEGRATOR_DIRECT ? "direct" : B.cfg.integrator == BLING_INTEGRATOR_BIDIR ? "bidir" : "path")
+       << (B.cfg.renderer == BLING_RENDERER_LIGHT ? "light" : B.cfg.renderer == BLING_RENDERER_METROPOLIS ? "metropolis" : B.cfg.renderer != BLING_RENDERER_SAMPLER_PATH ? "other" : B.cfg.integrator == BLING_INTEGRATOR_DIRECT ? "direct" : B.cfg.integrator == BLING_INTEGRATOR_BIDIR ? "bidir" : "path")
        << " md=" << B.cfg.max_depth
        << " sd=" << B.cfg.sample_depth << " sampler "
        << (B.cfg.sampler == BLING_SAMPLER_STRATIFIED ? "stratified " : "random ") << B.cfg.nu << "x"
@@ -1429,6 +1457,7 @@ int bling_host_load(const char* path, const char* overrides, bling_host_scene** 
 const bling_scene_desc* bling_host_desc(const bling_host_scene* s) { return s ? &s->b.desc : nullptr; }
 void bling_host_config(const bling_host_scene* s, bling_render_config* out) { *out = s->b.desc.config; }
 void bling_host_light(const bling_host_scene* s, bling_light_tracer* out) { *out = s->b.desc.light; }
+void bling_host_metropolis(const bling_host_scene* s, bling_metropolis* out) { *out = s->b.desc.metropolis; }
 void bling_host_filter_size(const bling_host_scene* s, float* wh) { wh[0] = s->b.desc.filter.width; wh[1] = s->b.desc.filter.height; }
 void bling_host_filter_table(const bling_host_scene* s, float* out256) {
   std::memcpy(out256, s->b.desc.filter.table, sizeof s->b.desc.filter.table);

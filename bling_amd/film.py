@@ -52,6 +52,23 @@ def write_hdr(path: str, film, w: int, h: int) -> None:
         raise OSError(_ffi.host().bling_host_last_error().decode())
 
 
+def mlt_bnext(p: int, b, b_new) -> np.float32:
+    """bnext = lerp (1 / p) b bNew (Metropolis.hs:115, Math.hs:108-110) in binary32; b starts at 1."""
+    t = np.float32(1) / np.float32(p)
+    return np.float32(np.float32((np.float32(1) - t) * np.float32(b)) + np.float32(t * np.float32(b_new)))
+
+
+def mlt_image(splat, bs, w: int, h: int) -> np.ndarray:
+    """The Metropolis renderer's image after pass p = len(bs) (Metropolis.hs:117): getPixel of an empty
+    film with the accumulated splat image (h * w * 3 XYZ) and the splat weight bnext / p, where bnext
+    runs over the passes' b' values bs; linear RGB (h, w, 3)."""
+    from .scene import film_splat_to_rgb
+    b = np.float32(1)
+    for p, bn in enumerate(bs, 1):
+        b = mlt_bnext(p, b, bn)
+    return film_splat_to_rgb(None, splat, np.float32(b / np.float32(len(bs))), w, h)
+
+
 def progress_writer(base: str, w: int, h: int):
     """progressWriter: a ProgressReporter (bling_amd.render.Progress -> bool) that writes every
     completed pass to ``<base>-NNNNN.png`` and ``.hdr`` and asks to continue."""

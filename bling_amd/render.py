@@ -25,6 +25,10 @@ DEFAULT_SEED = 0x0B11A6   # master seed of the benchmark
 LIGHT_RECORD = np.dtype([("photon", "<u4"), ("depth", "<u4"), ("sx", "<i4"), ("sy", "<i4"),
                          ("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("pad", "<u4")])
 
+# numpy view of bling_mlt_record (include/bling.h)
+MLT_RECORD = np.dtype([("chain", "<u4"), ("mutation", "<u4"), ("x", "<f4"), ("y", "<f4"), ("i_prop", "<f4"),
+                       ("a", "<f4"), ("flags", "<u4"), ("pad", "<u4")])
+
 
 class BlingError(RuntimeError):
     def __init__(self, rc: int, msg: str):
@@ -35,6 +39,15 @@ class BlingError(RuntimeError):
 def _check(rc: int):
     if rc != 0:
         raise BlingError(rc, _ffi.hip().bling_last_error().decode())
+
+
+def mlt_boot(values, seed, pass_index, chains):
+    """bling_debug_mlt_boot: (b', start samples) of hand-given bootstrap contributions; no device needed."""
+    v = np.ascontiguousarray(values, np.float32)
+    b = np.zeros(1, np.float32)
+    starts = np.zeros(chains, np.uint32)
+    _check(_ffi.hip().bling_debug_mlt_boot(_ffi.f32ptr(v), len(v), seed, pass_index, chains, _ffi.f32ptr(b), _ffi.u32ptr(starts)))
+    return np.float32(b[0]), starts
 
 
 class Context:
@@ -355,6 +368,41 @@ class Context:
                                              rec.ctypes.data_as(C.POINTER(_ffi.LightRecord)), cap, C.byref(n)))
         return rec[:n.value]
 
+    def mlt_pass(self, seed=DEFAULT_SEED, pass_index=1, splat: np.ndarray | None = None):
+        """One pass of the Metropolis renderer (Renderer/Metropolis.hs:76-120) into a host splat image
+        (X,Y,Z), accumulated.  Returns (splat, MltStats); MltStats.b is the pass's b'."""
+        job = self.job
+        if splat is None:
+            splat = np.zeros(job.width * job.height * 3, np.float32)
+        st = _ffi.MltStats()
+        _check(_ffi.hip().bling_mlt_pass(self._h, seed, pass_index, _ffi.f32ptr(splat), C.byref(st)))
+        return splat, st
+
+    def mlt_records(self, seed=DEFAULT_SEED, pass_index=1, first_chain=0, n_chains=None, cap=None):
+        """bling_debug_mlt_records: (records sorted by (chain, mutation), the chains' start samples, b').
+        Without cap the buffer is sized by a first counting call; a given cap that is too small raises."""
+        if n_chains is None:
+            n_chains = self.job.metropolis.chains - first_chain
+        lib = _ffi.hip()
+        n = C.c_size_t()
+        if cap is None:
+            rc = lib.bling_debug_mlt_records(self._h, seed, pass_index, first_chain, n_chains, None, 0, C.byref(n), None, None)
+            if rc != 0 and n.value == 0:
+                _check(rc)
+            cap = n.value
+        rec = np.zeros(cap, MLT_RECORD)
+        starts = np.zeros(n_chains, np.uint32)
+        b = np.zeros(1, np.float32)
+        _check(lib.bling_debug_mlt_records(self._h, seed, pass_index, first_chain, n_chains,
+                                           rec.ctypes.data_as(C.POINTER(_ffi.MltRecord)), cap, C.byref(n),
+                                           _ffi.u32ptr(starts), _ffi.f32ptr(b)))
+        return rec[:n.value], starts, np.float32(b[0])
+
+    def mlt_set_boot(self, values=None):
+        """bling_debug_mlt_set_boot: bootstrap contributions that replace the evaluated ones (None: off)."""
+        v = np.zeros(0, np.float32) if values is None else np.ascontiguousarray(values, np.float32)
+        _check(_ffi.hip().bling_debug_mlt_set_boot(self._h, _ffi.f32ptr(v) if len(v) else None, len(v)))
+
     def close(self):
         if self._h:
             _ffi.hip().bling_destroy(self._h)
@@ -455,7 +503,38 @@ class LightTracerRenderer:
         return film, splat
 
 
+class MetropolisRenderer:
+    """``instance Renderer Metropolis`` (Renderer/Metropolis.hs:59-120) on the MI355X core: passes 1, 2,
+    ... until the reporter returns False; each PassDone carries the (empty) film, the accumulated splat
+    image and the splat weight bnext / p of `PassDone p img' (bnext / p)` (:115-117)."""
+
+    def __init__(self, device: int = 0, seed: int = DEFAULT_SEED):
+        self.device = device
+        self.seed = seed
+
+    def render(self, job: Job, report):
+        from .film import mlt_bnext
+        ctx = Context(self.device)
+        ctx.upload(job)
+        film = np.zeros(job.width * job.height * 4, np.float32)
+        splat = np.zeros(job.width * job.height * 3, np.float32)
+        report(Progress("Started"))
+        p, b = 1, np.float32(1)
+        while True:
+            splat, st = ctx.mlt_pass(seed=self.seed, pass_index=p, splat=splat)
+            b = mlt_bnext(p, b, st.b)
+            info = st.as_dict()
+            info["splat"] = splat
+            info["splat_weight"] = float(np.float32(b / np.float32(p)))
+            if not report(Progress("PassDone", p, film, info)):
+                break
+            p += 1
+        ctx.close()
+        return film, splat
+
+
 RENDERER_LIGHT = 3   # BLING_RENDERER_LIGHT (include/bling_scene.h)
+RENDERER_METROPOLIS = 4   # BLING_RENDERER_METROPOLIS
 
 
 def render(job: Job, passes: int = 1, device: int = 0, seed: int = DEFAULT_SEED) -> np.ndarray:
@@ -476,4 +555,15 @@ def render(job: Job, passes: int = 1, device: int = 0, seed: int = DEFAULT_SEED)
         film, splat = LightTracerRenderer(device, seed).render(job, rep)
         sw = np.float32(1.0) / np.float32(count["n"] * job.light.pass_photons)
         return film_splat_to_rgb(film, splat, sw, job.width, job.height)
+    if job.config.renderer == RENDERER_METROPOLIS:
+        from .scene import film_splat_to_rgb
+        last = {}
+
+        def rep_mlt(pr: Progress) -> bool:
+            if pr.kind == "PassDone":
+                last["sw"] = pr.stats["splat_weight"]
+            return rep(pr)
+
+        film, splat = MetropolisRenderer(device, seed).render(job, rep_mlt)
+        return film_splat_to_rgb(film, splat, np.float32(last["sw"]), job.width, job.height)
     return SamplerRenderer(device, seed).render(job, rep)

@@ -81,6 +81,18 @@ BIDIR_SCENES = {
 }
 
 
+# The Metropolis renderer (`renderer { metropolis ... directSamples 0 }`, override
+# metropolis=maxDepth,mpp,bootstrap,plarge[,chains] and chains=N) on scenes of this repository, for its
+# parity tests (tests/test_gpu_mlt.py).
+MLT_SCENES = {
+    "M1": BenchConfig("M1", "cornell-box.bling", "image=48,48;metropolis=5,0.25,100,0.25,64", 0),      # one light, all-LDS profile
+    "M2": BenchConfig("M2", "direct-lighting.bling", "image=24,24;metropolis=5,0.25,100,0.25,65", 0),  # glass and mirror
+    "M3": BenchConfig("M3", "delta-lights.bling", "image=24,24;metropolis=5,0.25,100,0.25,65", 0),     # point / directional lights
+    "M4": BenchConfig("M4", "sun-sky.bling", "image=48,27;metropolis=5,0.25,100,0.25,257", 0),         # infinite light, escaping rays
+    "M5": BenchConfig("M5", "procedural-textures.bling", "image=24,24;metropolis=5,0.25,100,0.25,65", 0),  # computed textures
+}
+
+
 class Job:
     """A parsed `.bling` job: RenderJob + the sampler/path renderer configuration."""
 
@@ -100,6 +112,9 @@ class Job:
         lt = _ffi.LightTracer()
         lib.bling_host_light(h, C.byref(lt))
         self.light = lt                     # passPhotons, w2r, pixel_area (bling_light_tracer)
+        mp = _ffi.Metropolis()
+        lib.bling_host_metropolis(h, C.byref(mp))
+        self.metropolis = mp                # maxDepth, mpp, bootstrap, plarge, chains (bling_metropolis)
         fw = np.zeros(2, np.float32)
         lib.bling_host_filter_size(h, _ffi.f32ptr(fw))
         self.filter_size = (float(fw[0]), float(fw[1]))
@@ -188,7 +203,7 @@ def parse_job(path: str, overrides: str | None = None) -> Job:
 
 
 def load_config(name: str, overrides_extra: str | None = None) -> Job:
-    c = CONFIGS[name] if name in CONFIGS else BIDIR_SCENES[name] if name in BIDIR_SCENES else FEATURE_SCENES[name]
+    c = CONFIGS[name] if name in CONFIGS else BIDIR_SCENES[name] if name in BIDIR_SCENES else MLT_SCENES[name] if name in MLT_SCENES else FEATURE_SCENES[name]
     ov = ";".join(x for x in (c.overrides, overrides_extra) if x)
     return Job(c.path, ov or None)
 

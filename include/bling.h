@@ -333,6 +333,57 @@ typedef struct bling_light_record {
 int bling_debug_light_records(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, uint32_t first_photon,
                               uint32_t n_photons, bling_light_record* records, size_t cap, size_t* n);
 
+/* ---- Metropolis renderer (Renderer/Metropolis.hs) over the bidirectional integrator ---- */
+typedef struct bling_mlt_stats {
+    double   b;                /* this pass's b' = sum I / bootstrap (a binary32 value)           */
+    uint64_t mutations;        /* M = floor (mpp * nPixels), over all chains                      */
+    uint64_t large_steps;      /* mutations whose large-step draw was < plarge                    */
+    uint64_t accepted;
+    uint64_t splats;           /* splats inside the image, finite                                 */
+    uint64_t dropped;          /* NaN / Inf splats inside the image, skipped (Image.hs:201-221)   */
+    uint64_t rays_camera, rays_continuation, rays_mis, rays_shadow, path_vertices;   /* as bling_stats,
+                                  over the bootstrap samples, the chains' first evaluation and the
+                                  mutations                                                        */
+    double   ms_total;         /* device time of the pass (HIP events)                           */
+} bling_mlt_stats;
+
+/* Replaces: one pass of `instance Renderer Metropolis` (Renderer/Metropolis.hs:76-120) for a scene
+ * whose renderer block is `metropolis maxDepth N mpp F bootstrap N plarge F directSamples 0`:
+ * the bootstrap (:142-169), then M = floor (mpp * nPixels) mutations over `chains` independent chains
+ * (chain c does M div C, plus one if c < M mod C; chains = 1 is the reference's one chain), each
+ * splatting the current and the proposed sample (:96-104) into splat_inout: W*H*3 XYZ, host,
+ * ACCUMULATED into, may be NULL.  pass_index numbers passes from 1.  The reference's image after pass
+ * p is getPixel of an empty film with splat weight bnext / p, bnext = lerp (1 / p) b b' from b = 1
+ * (:115-117); stats->b is this pass's b'.  Errors: BLING_ENOSCENE without a scene; BLING_EINVAL when
+ * the scene's renderer is not this one, the context holds several devices, or the bootstrap selection
+ * lands where the reference stops with an error (a slot a NaN bootstrap sample left unwritten). */
+int bling_mlt_pass(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, float* splat_inout, bling_mlt_stats* stats);
+
+/* Parity hook: one record per (chain, mutation) of chains first_chain .. first_chain + n_chains - 1 of
+ * that pass, sorted by that pair; nothing is accumulated.  starts (may be NULL) receives n_chains
+ * bootstrap sample indices, the chains' start samples; *b (may be NULL) the pass's b'.  *n receives the
+ * number of records; a capacity smaller than *n is BLING_EINVAL (with *n set). */
+typedef struct bling_mlt_record {
+    uint32_t chain, mutation;
+    float    x, y;             /* the proposal's imageX, imageY                                   */
+    float    i_prop, a;        /* evalI of the proposal, min 1 (iProp / iCurr) (NaN where GHC's is) */
+    uint32_t flags;            /* bit 0: large step, bit 1: accepted                              */
+    uint32_t pad;
+} bling_mlt_record;
+int bling_debug_mlt_records(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, uint32_t first_chain, uint32_t n_chains,
+                            bling_mlt_record* records, size_t cap, size_t* n, uint32_t* starts, float* b);
+
+/* Probe of the pass's host bookkeeping (bootstrap, Metropolis.hs:150-167), without a context or a device:
+ * from n bootstrap contributions I it forms *b = sum I / n (a NaN counts 0) and every chain's start sample
+ * (starts: `chains` bootstrap sample indices), with the pass's own keys.  BLING_EINVAL, with the reason,
+ * where a chain's selection reads a slot that a NaN sample left unwritten. */
+int bling_debug_mlt_boot(const float* I, uint32_t n, uint32_t seed, uint32_t pass_index, uint32_t chains, float* b,
+                         uint32_t* starts);
+/* Test hook: the following bling_mlt_pass / bling_debug_mlt_records calls of this context take these n
+ * values for the bootstrap contributions when n equals the scene's bootstrap (the samples are still
+ * evaluated); n = 0 or a scene upload ends it. */
+int bling_debug_mlt_set_boot(bling_ctx* ctx, const float* I, uint32_t n);
+
 /* Diagnostics (no reference counterpart): the path-state bytes the shading kernel k_shade moved in
  * the context's last bling_render_pass*, per stream and direction -- out[2 k] read, out[2 k + 1]
  * written, stream k in the order BLING_STREAM_NAMES lists -- counted where the algorithm needs

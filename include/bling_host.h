@@ -32,6 +32,7 @@ void bling_host_config(const bling_host_scene* s, bling_render_config* out);
 void bling_host_filter_size(const bling_host_scene* s, float* wh);
 /* The light tracer block: photons per pass, and the camera's world-to-raster matrix and pixel area. */
 void bling_host_light(const bling_host_scene* s, bling_light_tracer* out);
+void bling_host_metropolis(const bling_host_scene* s, bling_metropolis* out);
 /* The 16x16 filter table (mkTableFilter, Image.hs:48-61) and the scene's prim/shape/light counts
  * (out[0..5] = triangles, shapes, fractal present, prims, lights, feature bits) for tests/tools. */
 void bling_host_filter_table(const bling_host_scene* s, float* out256);

@@ -237,9 +237,11 @@ typedef struct bling_filter {
 enum bling_sampler_kind { BLING_SAMPLER_STRATIFIED = 0, BLING_SAMPLER_RANDOM = 1 };
 enum bling_renderer_kind {
     BLING_RENDERER_SAMPLER_PATH = 0,   /* sampler renderer (Rendering.hs:77-78) + surface integrator      */
-    BLING_RENDERER_OTHER = 1,          /* metropolis: not served                                           */
+    BLING_RENDERER_OTHER = 1,          /* metropolis with directSamples > 0: not served (`undefined` in the reference) */
     BLING_RENDERER_SPPM = 2,           /* sppm photonCount maxDepth radius [alpha] (RendererParser.hs:40-45) */
-    BLING_RENDERER_LIGHT = 3           /* light passPhotons N (RendererParser.hs:47-50, Renderer/LightTracer.hs) */
+    BLING_RENDERER_LIGHT = 3,          /* light passPhotons N (RendererParser.hs:47-50, Renderer/LightTracer.hs) */
+    BLING_RENDERER_METROPOLIS = 4      /* metropolis maxDepth mpp bootstrap plarge directSamples <= 0
+                                          (RendererParser.hs:32-38, Renderer/Metropolis.hs)                */
 };
 /* the sampler renderer's surface integrator (IO/IntegratorParser.hs:15-47) */
 enum bling_integrator_kind {
@@ -274,6 +276,17 @@ typedef struct bling_light_tracer {
     float   pixel_area;        /* ap = pw * ph                                                 */
     float   w2r[16];           /* world -> raster, row-major                                   */
 } bling_light_tracer;
+
+/* ---- Metropolis renderer (Renderer/Metropolis.hs; BLING_RENDERER_METROPOLIS only) ----
+ * The chain is evaluated with mkBidirPathIntegrator maxDepth maxDepth (:46-49); a pass does
+ * floor (mpp * nPixels) mutations, split over `chains` independent chains (chains = 1: the reference). */
+typedef struct bling_metropolis {
+    int32_t max_depth;         /* 1 .. 16, the bidirectional integrator's maxDepth and sampleDepth */
+    float   mpp;               /* mutations per pixel                                          */
+    int32_t bootstrap;         /* bootstrap samples per pass, >= 1                             */
+    float   plarge;            /* probability of a large step                                  */
+    int32_t chains;            /* >= 1; the loader's default is 4096, capped at the mutations  */
+} bling_metropolis;
 
 typedef struct bling_scene_desc {
     /* triangles (TriangleMesh.hs:39-60; vertices already transformed to world space) */
@@ -317,6 +330,8 @@ typedef struct bling_scene_desc {
 
     /* trailing member: everything above keeps its offset */
     bling_light_tracer light;
+    /* appended after it the same way */
+    bling_metropolis metropolis;
 } bling_scene_desc;
 
 #ifdef __cplusplus
