@@ -2621,6 +2621,16 @@ void oracle_light_sample_probe(oracle_scene* os, int li, const float* p3, float 
   out[20] = ls.ray.o.x; out[21] = ls.ray.o.y; out[22] = ls.ray.o.z;
   out[23] = ls.ray.d.x; out[24] = ls.ray.d.y; out[25] = ls.ray.d.z; out[26] = ls.ray.tmin; out[27] = ls.ray.tmax;
 }
+// Light.sample' (Light.hs:166-213) of light `li`: out12 = ray origin, ray direction, normal at the
+// light, pdf, ray tmin, 1 if Le is not black
+void oracle_light_ray_probe(oracle_scene* os, int li, float uo1, float uo2, float ud1, float ud2, float* out) {
+  const Scene& Sc = os->s;
+  LightRay r = light_ray(Sc, Sc.d->lights[li], uo1, uo2, ud1, ud2);
+  out[0] = r.ray.o.x; out[1] = r.ray.o.y; out[2] = r.ray.o.z;
+  out[3] = r.ray.d.x; out[4] = r.ray.d.y; out[5] = r.ray.d.z;
+  out[6] = r.n.x; out[7] = r.n.y; out[8] = r.n.z;
+  out[9] = r.pdf; out[10] = r.ray.tmin; out[11] = is_black(r.li) ? 0.f : 1.f;
+}
 float oracle_light_pdf_probe(oracle_scene* os, int li, const float* p3, const float* wi3) {
   const Scene& Sc = os->s;
   return light_pdf(Sc, Sc.d->lights[li], mk(p3[0], p3[1], p3[2]), mk(wi3[0], wi3[1], wi3[2]));

@@ -84,6 +84,7 @@ def lib() -> C.CDLL:
         L.oracle_light_sample_probe.argtypes = [C.c_void_p, C.c_int, f32p, C.c_float, C.c_float, C.c_float, f32p]
         L.oracle_light_pdf_probe.argtypes = [C.c_void_p, C.c_int, f32p, f32p]
         L.oracle_light_pdf_probe.restype = C.c_float
+        L.oracle_light_ray_probe.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, f32p]
         L.oracle_env_probe.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, f32p]
         L.oracle_fire_ray_probe.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, f32p]
         L.oracle_stex_probe.argtypes = [C.c_void_p, C.c_int, f32p]
