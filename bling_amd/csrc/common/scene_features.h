@@ -12,7 +12,8 @@ enum : uint32_t {
   GRAPHPAPER = 1u << 5, AREA = 1u << 6, ENV_CONST = 1u << 7, ENV_SKY = 1u << 8,
   SPHERE = 1u << 9, TRI_NORMALS = 1u << 10, FRACTAL = 1u << 11, TRIS = 1u << 12,
   SHAPES2 = 1u << 13, TRANSMATTE = 1u << 14, SHINYMETAL = 1u << 15, SUBSTRATE = 1u << 16, BUMP = 1u << 17,
-  PROCTEX = 1u << 18,                // per-hit computed spectra (blend / gradient / checker), cellNoise, crystal
+  PROCTEX = 1u << 18,                // per-hit computed spectra (blend / gradient / checker), cellNoise, crystal,
+                                      // textured material parameters beyond substrate's scalars
   DELTA = 1u << 19,                   // point / directional lights (delta distributions)
   ENV_IMG = 1u << 20,                 // infinite lights with an image map
   MULTI_LIGHT = 1u << 21              // more than one light (the one-light profile's kernels read light 0)
@@ -33,6 +34,16 @@ inline uint32_t scene_features(const bling_scene_desc* d) {
       default: break;
     }
     if (d->materials[i].stex[3] >= 0) f |= BUMP;
+    // parameters the all-features kernels evaluate or transform at the hit (bling_scene.h, "materials")
+    const bling_material& m = d->materials[i];
+    if (m.kind == BLING_MAT_SUBSTRATE) {
+      for (int j = 0; j < 3; ++j)
+        if (m.tex[j] >= 0 && (uint32_t)m.tex[j] < d->num_textures && d->textures[m.tex[j]].kind != BLING_TEX_CONST) f |= PROCTEX;
+    } else if (m.kind != BLING_MAT_BLACKBODY) {
+      if (m.stex[0] >= 0) f |= PROCTEX;
+      if ((m.kind == BLING_MAT_TRANSMATTE || m.kind == BLING_MAT_SHINYMETAL) &&
+          (m.stex[1] == BLING_SLOT_RAW || m.stex[2] == BLING_SLOT_RAW)) f |= PROCTEX;
+    }
   }
   for (uint32_t i = 0; i < d->num_textures; ++i) {
     if (d->textures[i].kind == BLING_TEX_GRAPHPAPER) f |= GRAPHPAPER;

@@ -159,7 +159,7 @@ DEV void bd_walks(const DevScene& S, const LdsScene& L, const BdBufs& B, uint32_
       float eps;
       int mat, hit_light;
       hit_geometry<F>(S, ray, hv, dgg, dgs, eps, mat, hit_light);
-      float ttmp[(F & FT_PROCTEX) ? 32 : 1];
+      float ttmp[bsdf_tmp_floats<F>()];
       const Bsdf bsdf = make_bsdf<F>(S, mat, dgg, dgs, ttmp);
       const float ubc = rnd1(S, k, (adj ? 4 : 3) + 12 * depth);       // :162, :173
       float u1, u2; rnd2(S, k, (adj ? 5 : 4) + 9 * depth, &u1, &u2);
@@ -326,7 +326,7 @@ static __global__ __launch_bounds__(256) void k_bd_connect(const DevScene* __res
       Sp inner = sconst(0.f);
       if (!((lm >> s) & 1u)) {                                       // :118 (every term of a specular s is black)
         const size_t la = bd_at(B, B.md + s, sid);
-        float tmp_a[(F & FT_PROCTEX) ? 32 : 1];
+        float tmp_a[bsdf_tmp_floats<F>()];
         float eps_a;
         const Bsdf ba = bd_vertex_bsdf<F>(S, B, la, tmp_a, eps_a);
         const float4 wa4 = B.vwo[la];
@@ -338,7 +338,7 @@ static __global__ __launch_bounds__(256) void k_bd_connect(const DevScene* __res
           Sp c = sconst(0.f);
           if (!((em >> t) & 1u)) {                                   // :119
             const size_t ea = bd_at(B, t, sid);
-            float tmp_b[(F & FT_PROCTEX) ? 32 : 1];
+            float tmp_b[bsdf_tmp_floats<F>()];
             float eps_b;
             const Bsdf bb = bd_vertex_bsdf<F>(S, B, ea, tmp_b, eps_b);
             const V3 pe = ba.p, pl = bb.p;

@@ -148,18 +148,43 @@ void validate_scene(const bling_scene_desc* d) {
     if (!ok) throw std::invalid_argument("scalar texture " + std::to_string(k) + ": malformed");
   }
   for (uint32_t k = 0; k < d->num_materials; ++k) {
-    // transMatte / shinyMetal / substrate spectra are folded on the host (sClamp, conductor terms):
-    // make_bsdf reads their textures' constant values directly, so nothing computed may sit there
+    // the encoding of bling_scene.h ("materials"): every texture a kind reads is in range; a scalar
+    // slot's stex is a scalar texture or -1; a transformed spectrum slot is either folded (a constant
+    // record make_bsdf reads directly) or raw (any texture eval_spectrum serves at the top of a slot,
+    // which the texture loop above established for every record)
     const bling_material& m = d->materials[k];
-    int nt = 0;
-    if (m.kind == BLING_MAT_TRANSMATTE) nt = 2;
-    else if (m.kind == BLING_MAT_SHINYMETAL) nt = 4;
-    else if (m.kind == BLING_MAT_SUBSTRATE) nt = 3;
+    const std::string who = "material " + std::to_string(k);
+    int nt = 0, ns = 1;                                   // textures read, scalar slots with an stex
+    bool raw[4] = {true, true, true, true};               // untransformed slots take any texture
+    auto flag = [&](int j) {
+      if (m.stex[j] != -1 && m.stex[j] != BLING_SLOT_RAW) throw std::invalid_argument(who + ": bad raw-slot flag in stex[" + std::to_string(j) + "]");
+      return m.stex[j] == BLING_SLOT_RAW;
+    };
+    switch (m.kind) {
+      case BLING_MAT_BLACKBODY: ns = 0; break;
+      case BLING_MAT_MATTE: nt = 1; break;
+      case BLING_MAT_PLASTIC: case BLING_MAT_GLASS: case BLING_MAT_METAL: nt = 2; break;
+      case BLING_MAT_MIRROR: nt = 1; ns = 0; break;
+      case BLING_MAT_TRANSMATTE: nt = 2; raw[0] = raw[1] = flag(1); break;
+      case BLING_MAT_SHINYMETAL:
+        nt = 4; raw[0] = raw[1] = flag(1); raw[2] = raw[3] = flag(2);
+        if ((raw[0] && m.tex[0] != m.tex[1]) || (raw[2] && m.tex[2] != m.tex[3]))
+          throw std::invalid_argument(who + ": a raw shinyMetal spectrum must sit in both of its slots");
+        break;
+      case BLING_MAT_SUBSTRATE: nt = 3; ns = 3; break;    // raw or folded by the texture's kind
+      default: throw std::invalid_argument(who + ": unknown kind");
+    }
     for (int j = 0; j < nt; ++j) {
       const int32_t ti = m.tex[j];
-      if (ti < 0 || (uint32_t)ti >= d->num_textures || d->textures[ti].kind != BLING_TEX_CONST)
-        throw std::invalid_argument("material " + std::to_string(k) + ": texture " + std::to_string(j) +
-                                    " must be a constant spectrum (folded on the host)");
+      if (ti < 0 || (uint32_t)ti >= d->num_textures)
+        throw std::invalid_argument(who + ": texture " + std::to_string(j) + " out of range");
+      if (!raw[j] && d->textures[ti].kind != BLING_TEX_CONST)
+        throw std::invalid_argument(who + ": texture " + std::to_string(j) + " is marked folded but is no constant spectrum");
+    }
+    for (int j = 0; j < 4; ++j) {
+      if (!(j < ns || j == 3)) continue;                  // stex[3]: bump
+      if (m.stex[j] < -1 || (m.stex[j] >= 0 && (uint32_t)m.stex[j] >= d->num_scalar_textures))
+        throw std::invalid_argument(who + ": scalar texture " + std::to_string(j) + " out of range");
     }
   }
   // the path state packs a light index (and a hit light + 1) into 8 bits each (wavefront.h vf_*)

@@ -623,7 +623,46 @@ DEV const float* eval_spectrum(const DevScene& S, int ti, const DG& dg, float* t
   return eval_texture<F>(S, ti, dg.u, dg.v);
 }
 
-// tmp: 32 floats of the caller's that hold computed spectra (FT_PROCTEX profiles) while the Bsdf lives
+// Floats of the array a caller of make_bsdf keeps while the Bsdf lives: four spectra in the FT_PROCTEX
+// profiles (shinyMetal's two conductor pairs computed at the hit), nothing in the others
+constexpr int BSDF_TMP_FLOATS = 64;
+template <uint32_t F>
+constexpr int bsdf_tmp_floats() { return (F & FT_PROCTEX) ? BSDF_TMP_FLOATS : 1; }
+
+// sClamp's component (Spectrum.hs:453-456): max lo (min hi x) with GHC's comparisons (the loader's sclamp)
+DEV float sclamp1(float x, float lo, float hi) { const float y = x <= hi ? x : hi; return lo <= y ? y : lo; }
+
+// A material's scalar parameter 0 at the hit (ts dgs): the constant, or in the FT_PROCTEX profiles the
+// scalar texture of stex[0] (bling_scene.h, "materials")
+template <uint32_t F>
+DEV float mat_scalar0(const DevScene& S, const bling_material& m, const DG& dgs) {
+  if ((F & FT_PROCTEX) && m.stex[0] >= 0) return eval_stex<F>(S, m.stex[0], dgs.p, dgs.u, dgs.v);
+  return m.scalar[0];
+}
+
+// sClamp 0 1 (tex dgs) of a raw slot, formed into tmp (16 floats)
+template <uint32_t F>
+DEV const float* clamped_spectrum(const DevScene& S, int ti, const DG& dgs, float* tmp) {
+  const float* v = eval_spectrum<F>(S, ti, dgs, tmp);
+  SP_LOOP tmp[i] = sclamp1(v[i], 0.f, 1.f);
+  return tmp;
+}
+
+// frApproxEta / frApproxK (Fresnel.hs:72-78) of a raw slot's value, into eta and k (16 floats each);
+// the square root and the divisions are the correctly rounded ones the loader's folding uses
+template <uint32_t F>
+DEV void approx_conductor(const DevScene& S, int ti, const DG& dgs, float* eta, float* k) {
+  const float* v = eval_spectrum<F>(S, ti, dgs, eta);
+  SP_LOOP {
+    const float c = sclamp1(v[i], 0.f, 0.999f);
+    const float q = bcr::sqrt_f(c);
+    eta[i] = (1.f + q) / (1.f - q);
+    k[i] = bcr::sqrt_f(c / (1.f - c)) * 2.f;
+  }
+}
+
+// tmp: bsdf_tmp_floats<F>() floats of the caller's that hold computed spectra (FT_PROCTEX profiles)
+// while the Bsdf lives
 template <uint32_t F>
 DEV Bsdf make_bsdf(const DevScene& S, int mi, const DG& dgg, const DG& dgs_in, float* tmp = nullptr) {
   const int bump_tex = (F & FT_BUMP) ? gen(S.materials[mi]).stex[3] : -1;
@@ -646,7 +685,7 @@ DEV Bsdf make_bsdf(const DevScene& S, int mi, const DG& dgg, const DG& dgs_in, f
     BxDF b = z;
     b.r = eval_spectrum<F>(S, m.tex[0], dgs, tmp + 0);
     b.flags = F_REFL | F_DIFF;
-    float s = m.scalar[0];
+    float s = mat_scalar0<F>(S, m, dgs);                                               // s = ts dgs (Material.hs:40)
     if (s == 0.f) b.kind = K_LAMB;
     else {
       b.kind = K_OREN;
@@ -658,10 +697,10 @@ DEV Bsdf make_bsdf(const DevScene& S, int mi, const DG& dgg, const DG& dgs_in, f
   } else if ((F & FT_PLASTIC) && m.kind == BLING_MAT_PLASTIC) {
     BxDF d = z; d.kind = K_LAMB; d.flags = F_REFL | F_DIFF; d.r = eval_spectrum<F>(S, m.tex[0], dgs, tmp + 0);
     BxDF g = z; g.kind = K_MICRO; g.flags = F_REFL | F_GLOSSY; g.r = eval_spectrum<F>(S, m.tex[1], dgs, tmp + 16);
-    g.e = fix_exponent(1.f / m.scalar[0]); g.fr = FR_DIEL; g.ei = 1.0f; g.et = 1.5f;
+    g.e = fix_exponent(1.f / mat_scalar0<F>(S, m, dgs)); g.fr = FR_DIEL; g.ei = 1.0f; g.et = 1.5f;
     l0 = d; l1 = g; n = 2;
   } else if ((F & FT_GLASS) && m.kind == BLING_MAT_GLASS) {
-    float ior = m.scalar[0];
+    float ior = mat_scalar0<F>(S, m, dgs);                                             // ior = iort dgs
     BxDF rf = z; rf.kind = K_SREFL; rf.flags = F_REFL | F_SPEC; rf.r = eval_spectrum<F>(S, m.tex[0], dgs, tmp + 0);
     rf.clamp01 = true; rf.fr = FR_DIEL; rf.ei = 1.f; rf.et = ior;
     BxDF tr = z; tr.kind = K_STRANS; tr.flags = F_TRANS | F_SPEC; tr.r = eval_spectrum<F>(S, m.tex[1], dgs, tmp + 16);
@@ -669,14 +708,22 @@ DEV Bsdf make_bsdf(const DevScene& S, int mi, const DG& dgg, const DG& dgs_in, f
     l0 = rf; l1 = tr; n = 2;
   } else if ((F & FT_METAL) && m.kind == BLING_MAT_METAL) {
     BxDF g = z; g.kind = K_MICRO; g.flags = F_REFL | F_GLOSSY; g.r = nullptr;
-    g.e = fix_exponent(1.f / m.scalar[0]); g.fr = FR_COND;
+    g.e = fix_exponent(1.f / mat_scalar0<F>(S, m, dgs)); g.fr = FR_COND;
     g.eta = eval_spectrum<F>(S, m.tex[0], dgs, tmp + 0); g.k = eval_spectrum<F>(S, m.tex[1], dgs, tmp + 16);
     l0 = g; n = 1;
   } else if ((F & FT_TRANSMATTE) && m.kind == BLING_MAT_TRANSMATTE) {
-    // translucentMatte (Material.hs:43-53): r and t folded on the host (bling_scene.h)
+    // translucentMatte (Material.hs:43-53): r and t folded on the host, or formed here from the raw
+    // kr / kt (bling_scene.h): r = sClamp 0 1 (kr dgs), t = sClamp 0 1 (kt dgs) * (white - r)
     BxDF rf = z, tr = z;
-    rf.r = gen(S.textures[m.tex[0]]).value; tr.r = gen(S.textures[m.tex[1]]).value;
-    float s = m.scalar[0];
+    if ((F & FT_PROCTEX) && m.stex[1] == BLING_SLOT_RAW) {
+      rf.r = clamped_spectrum<F>(S, m.tex[0], dgs, tmp + 0);
+      const float* kt = eval_spectrum<F>(S, m.tex[1], dgs, tmp + 16);
+      SP_LOOP tmp[16 + i] = sclamp1(kt[i], 0.f, 1.f) * (1.f - tmp[i]);
+      tr.r = tmp + 16;
+    } else {
+      rf.r = gen(S.textures[m.tex[0]]).value; tr.r = gen(S.textures[m.tex[1]]).value;
+    }
+    float s = mat_scalar0<F>(S, m, dgs);                                               // s = ks dgs
     if (s == 0.f) { rf.kind = K_LAMB; tr.kind = K_LAMB; }
     else {
       float sg = clampf(s, 0.f, 1.f), sig2 = sg * sg;
@@ -687,17 +734,34 @@ DEV Bsdf make_bsdf(const DevScene& S, int mi, const DG& dgg, const DG& dgs_in, f
     tr.flags = F_TRANS | F_DIFF; tr.btdf = true;                                       // bxdfTypeFlip (Refl|Trans)
     l0 = rf; l1 = tr; n = 2;
   } else if ((F & FT_SHINYMETAL) && m.kind == BLING_MAT_SHINYMETAL) {
-    // mkShinyMetal (Material.hs:98-109): conductor spectra folded on the host
+    // mkShinyMetal (Material.hs:98-109): conductor spectra folded on the host, or formed here from
+    // the raw ks (glossy lobe) / kr (specular lobe) (bling_scene.h)
     BxDF g = z; g.kind = K_MICRO; g.flags = F_REFL | F_GLOSSY; g.r = nullptr;
-    g.e = fix_exponent(1.f / m.scalar[0]); g.fr = FR_COND;
-    g.eta = gen(S.textures[m.tex[0]]).value; g.k = gen(S.textures[m.tex[1]]).value;
+    g.e = fix_exponent(1.f / mat_scalar0<F>(S, m, dgs)); g.fr = FR_COND;
+    if ((F & FT_PROCTEX) && m.stex[1] == BLING_SLOT_RAW) {
+      approx_conductor<F>(S, m.tex[0], dgs, tmp + 0, tmp + 16);
+      g.eta = tmp + 0; g.k = tmp + 16;
+    } else {
+      g.eta = gen(S.textures[m.tex[0]]).value; g.k = gen(S.textures[m.tex[1]]).value;
+    }
     BxDF sp = z; sp.kind = K_SREFL; sp.flags = F_REFL | F_SPEC; sp.r = nullptr; sp.fr = FR_COND;
-    sp.eta = gen(S.textures[m.tex[2]]).value; sp.k = gen(S.textures[m.tex[3]]).value;
+    if ((F & FT_PROCTEX) && m.stex[2] == BLING_SLOT_RAW) {
+      approx_conductor<F>(S, m.tex[2], dgs, tmp + 32, tmp + 48);
+      sp.eta = tmp + 32; sp.k = tmp + 48;
+    } else {
+      sp.eta = gen(S.textures[m.tex[2]]).value; sp.k = gen(S.textures[m.tex[3]]).value;
+    }
     l0 = g; l1 = sp; n = 2;
   } else if ((F & FT_SUBSTRATE) && m.kind == BLING_MAT_SUBSTRATE) {
-    // mkSubstrate (Material.hs:111-128): one FresnelBlend lobe, spectra and exponents folded on the host
+    // mkSubstrate (Material.hs:111-128): one FresnelBlend lobe, spectra and exponents folded on the
+    // host; a slot whose texture is no constant is raw: sClamp 0 1 of its value at the hit (bling_scene.h)
     BxDF fb = z; fb.kind = K_FBLEND; fb.flags = F_REFL | F_GLOSSY;
     fb.r = gen(S.textures[m.tex[0]]).value; fb.eta = gen(S.textures[m.tex[1]]).value; fb.k = gen(S.textures[m.tex[2]]).value;
+    if (F & FT_PROCTEX) {
+      if (gen(S.textures[m.tex[0]]).kind != BLING_TEX_CONST) fb.r = clamped_spectrum<F>(S, m.tex[0], dgs, tmp + 0);
+      if (gen(S.textures[m.tex[1]]).kind != BLING_TEX_CONST) fb.eta = clamped_spectrum<F>(S, m.tex[1], dgs, tmp + 16);
+      if (gen(S.textures[m.tex[2]]).kind != BLING_TEX_CONST) fb.k = clamped_spectrum<F>(S, m.tex[2], dgs, tmp + 32);
+    }
     fb.e = m.scalar[0]; fb.A = m.scalar[1]; fb.B = m.scalar[2];
     // per-hit parameters: u / v = max 0 (t dgs), exponents fixExponent (1 / u); depth = td dgs
     if (m.stex[0] >= 0) { const float u = eval_stex<F>(S, m.stex[0], dgs.p, dgs.u, dgs.v); fb.e = fix_exponent(1.f / (0.f <= u ? u : 0.f)); }

@@ -1106,7 +1106,7 @@ DEV uint32_t shade_vertex(const DevScene& S, const WaveState& W, const PathSet& 
   DVREC3(W, sid, depth, 0, ray.o); DVREC3(W, sid, depth, 3, ray.d); DVREC(W, sid, depth, 6, hv.x);
   DVREC3(W, sid, depth, 10, dgg.n); DVREC(W, sid, depth, 13, eps);
   int intl_light = (spec && hit_light >= 0 && dot(dgg.n, ray.d) > 0.f) ? hit_light : -1;   // intLe rd (trap T6)
-  float ttmp[(F & FT_PROCTEX) ? 32 : 1];  // computed spectra of the BSDF (FT_PROCTEX profiles)
+  float ttmp[bsdf_tmp_floats<F>()];  // computed spectra of the BSDF (FT_PROCTEX profiles)
   Bsdf bsdf = make_bsdf<F>(S, mat, dgg, dgs, ttmp);
   V3 wo = -ray.d;
   V3 p = bsdf.p;
@@ -1399,7 +1399,7 @@ static __global__ __launch_bounds__(256) SHADE_OCC void k_shade_dl(const DevScen
       hit_geometry<F>(S, ray, hv, dgg, dgs, eps, mat, hit_light);
       const V3 wo = -ray.d;
       const int intl = (hit_light >= 0 && dot(dgg.n, wo) > 0.f) ? hit_light : -1;     // intLe int wo
-      float ttmp[(F & FT_PROCTEX) ? 32 : 1];  // computed spectra of the BSDF (FT_PROCTEX profiles)
+      float ttmp[bsdf_tmp_floats<F>()];  // computed spectra of the BSDF (FT_PROCTEX profiles)
       Bsdf bsdf = make_bsdf<F>(S, mat, dgg, dgs, ttmp);
       const V3 p = bsdf.p;
       vf = vf_make(intl, 0);

@@ -615,10 +615,12 @@ struct Parser {
     return c;
   }
 
-  float scalar_texture(const char* name) {              // pScalarTexture where a material folds a constant
-    float v = 0;
-    if (scalar_texture_any(name, &v) >= 0) L.fail(std::string(name) + ": only constant scalar textures are supported here");
-    return v;
+  // a material's scalar parameter k (pScalarTexture): a constant goes to scalar[k]; any other texture
+  // goes to stex[k] and is evaluated at the hit (make_bsdf)
+  void scalar_slot(bling_material& m, int k, const char* name) {
+    float v = 0.f;
+    m.stex[k] = scalar_texture_any(name, &v);
+    m.scalar[k] = v;
   }
 
   // pScalarTexture (MaterialParser.hs:115-156): returns -1 and the value for `constant`, else the
@@ -703,11 +705,13 @@ struct Parser {
     return (int)B.scalar_textures.size() - 1;
   }
 
-  // value of a constant spectrum texture; materials whose BxDF spectra are folded on the host
-  // (transMatte, shinyMetal) accept constant textures only
-  Spec const_texture(int ti, const char* what) {
+  // value of a constant spectrum texture.  Materials whose BxDF spectra are transformed (transMatte,
+  // shinyMetal, substrate) fold the transform here where its inputs are constant; a slot with any
+  // other texture keeps the raw texture index and the device transforms its value at the hit
+  // (BLING_SLOT_RAW, bling_scene.h)
+  bool is_const(int ti) const { return B.textures[ti].kind == BLING_TEX_CONST; }
+  Spec const_texture(int ti) {
     const bling_texture& tx = B.textures[ti];
-    if (tx.kind != BLING_TEX_CONST) L.fail(std::string(what) + ": only constant textures are supported");
     Spec s(16);
     for (int i = 0; i < 16; ++i) s[i] = tx.value[i];
     return s;
@@ -732,29 +736,38 @@ struct Parser {
     bling_material m{};
     m.tex[0] = m.tex[1] = m.tex[2] = m.tex[3] = -1;
     m.stex[0] = m.stex[1] = m.stex[2] = m.stex[3] = -1;
-    if (t == "matte") { m.kind = BLING_MAT_MATTE; m.tex[0] = spectrum_texture("kd"); m.scalar[0] = scalar_texture("sigma"); }
-    else if (t == "plastic") { m.kind = BLING_MAT_PLASTIC; m.tex[0] = spectrum_texture("kd"); m.tex[1] = spectrum_texture("ks"); m.scalar[0] = scalar_texture("rough"); }
-    else if (t == "glass") { m.kind = BLING_MAT_GLASS; m.scalar[0] = scalar_texture("ior"); m.tex[0] = spectrum_texture("kr"); m.tex[1] = spectrum_texture("kt"); }
-    else if (t == "metal") { m.kind = BLING_MAT_METAL; m.tex[0] = spectrum_texture("eta"); m.tex[1] = spectrum_texture("k"); m.scalar[0] = scalar_texture("rough"); }
+    if (t == "matte") { m.kind = BLING_MAT_MATTE; m.tex[0] = spectrum_texture("kd"); scalar_slot(m, 0, "sigma"); }
+    else if (t == "plastic") { m.kind = BLING_MAT_PLASTIC; m.tex[0] = spectrum_texture("kd"); m.tex[1] = spectrum_texture("ks"); scalar_slot(m, 0, "rough"); }
+    else if (t == "glass") { m.kind = BLING_MAT_GLASS; scalar_slot(m, 0, "ior"); m.tex[0] = spectrum_texture("kr"); m.tex[1] = spectrum_texture("kt"); }
+    else if (t == "metal") { m.kind = BLING_MAT_METAL; m.tex[0] = spectrum_texture("eta"); m.tex[1] = spectrum_texture("k"); scalar_slot(m, 0, "rough"); }
     else if (t == "mirror") { m.kind = BLING_MAT_MIRROR; m.tex[0] = spectrum_texture("kr"); }
     else if (t == "blackbody") { m.kind = BLING_MAT_BLACKBODY; }
     else if (t == "transMatte") {                          // pMatteTranslucent / translucentMatte
       int kr = spectrum_texture("kr"), kt = spectrum_texture("kt");
-      m.scalar[0] = scalar_texture("ks");
-      Spec r = sclamp(const_texture(kr, "transMatte kr"), 0.f, 1.f);      // sClamp 0 1 (kr dgs)
-      Spec tt = sclamp(const_texture(kt, "transMatte kt"), 0.f, 1.f);
-      Spec tr(16);
-      for (int i = 0; i < 16; ++i) tr[i] = tt[i] * (1.f - r[i]);          // sClamp 0 1 kt * (white - r)
+      scalar_slot(m, 0, "ks");
       m.kind = BLING_MAT_TRANSMATTE;
-      m.tex[0] = B.add_texture_const(r);
-      m.tex[1] = B.add_texture_const(tr);
+      if (is_const(kr) && is_const(kt)) {
+        Spec r = sclamp(const_texture(kr), 0.f, 1.f);                       // sClamp 0 1 (kr dgs)
+        Spec tt = sclamp(const_texture(kt), 0.f, 1.f);
+        Spec tr(16);
+        for (int i = 0; i < 16; ++i) tr[i] = tt[i] * (1.f - r[i]);          // sClamp 0 1 kt * (white - r)
+        m.tex[0] = B.add_texture_const(r);
+        m.tex[1] = B.add_texture_const(tr);
+      } else {                                             // t needs r: both stay raw
+        m.tex[0] = kr; m.tex[1] = kt; m.stex[1] = BLING_SLOT_RAW;
+      }
     } else if (t == "shinyMetal") {                        // pShinyMetal / mkShinyMetal
       int kr = spectrum_texture("kr"), ks = spectrum_texture("ks");
-      m.scalar[0] = scalar_texture("rough");
-      Spec r = const_texture(kr, "shinyMetal kr"), s = const_texture(ks, "shinyMetal ks");
+      scalar_slot(m, 0, "rough");
       m.kind = BLING_MAT_SHINYMETAL;
-      m.tex[0] = B.add_texture_const(fr_approx_eta(s)); m.tex[1] = B.add_texture_const(fr_approx_k(s));
-      m.tex[2] = B.add_texture_const(fr_approx_eta(r)); m.tex[3] = B.add_texture_const(fr_approx_k(r));
+      if (is_const(ks)) {
+        Spec s = const_texture(ks);
+        m.tex[0] = B.add_texture_const(fr_approx_eta(s)); m.tex[1] = B.add_texture_const(fr_approx_k(s));
+      } else { m.tex[0] = m.tex[1] = ks; m.stex[1] = BLING_SLOT_RAW; }
+      if (is_const(kr)) {
+        Spec r = const_texture(kr);
+        m.tex[2] = B.add_texture_const(fr_approx_eta(r)); m.tex[3] = B.add_texture_const(fr_approx_k(r));
+      } else { m.tex[2] = m.tex[3] = kr; m.stex[2] = BLING_SLOT_RAW; }
     }
     else if (t == "substrate") {                          // pSubstrateMaterial / mkSubstrate (Material.hs:111-128)
       int kd = spectrum_texture("kd"), ks = spectrum_texture("ks"), ka = spectrum_texture("ka");
@@ -764,10 +777,12 @@ struct Parser {
       m.stex[2] = scalar_texture_any("depth", &depth);
       auto fix_exponent = [](float e) { return (e > 10000.f || std::isnan(e)) ? 10000.f : e; };   // Microfacet.hs:128-130
       auto max0 = [](float x) { return 0.f <= x ? x : 0.f; };                                  // max 0 (GHC max)
+      // sClamp 0 1 of a constant is folded; any other texture stays raw (told apart by its kind)
+      auto clamped = [&](int ti) { return is_const(ti) ? B.add_texture_const(sclamp(const_texture(ti), 0.f, 1.f)) : ti; };
       m.kind = BLING_MAT_SUBSTRATE;
-      m.tex[0] = B.add_texture_const(sclamp(const_texture(kd, "substrate kd"), 0.f, 1.f));
-      m.tex[1] = B.add_texture_const(sclamp(const_texture(ks, "substrate ks"), 0.f, 1.f));
-      m.tex[2] = B.add_texture_const(sclamp(const_texture(ka, "substrate ka"), 0.f, 1.f));
+      m.tex[0] = clamped(kd);
+      m.tex[1] = clamped(ks);
+      m.tex[2] = clamped(ka);
       m.scalar[0] = fix_exponent(1.f / max0(ur));          // mkAnisotropic (1 / u) (1 / v)
       m.scalar[1] = fix_exponent(1.f / max0(vr));
       m.scalar[2] = depth;

@@ -101,7 +101,30 @@ typedef struct bling_image {
     const float* texels;       /* width * height * channels                                   */
 } bling_image;
 
-/* ---- materials (Material.hs:32-96) ---- */
+/* ---- materials (Material.hs:32-128) ----
+ * Every parameter of a material is a texture evaluated at the hit (Material.hs:32-128).
+ *
+ * Scalar parameters: a constant sits in scalar[k] with stex[k] = -1; any other scalar texture sits
+ * in stex[k] (scalar[k] = 0) and is evaluated per hit.  That is scalar[0] / stex[0] of matte (sigma),
+ * plastic, metal and shinyMetal (rough), glass (ior) and transMatte (ks), and scalar[0..2] /
+ * stex[0..2] of substrate.
+ *
+ * Spectrum parameters that reach the BxDF as they are (kd of matte / plastic, ks of plastic, kr / kt
+ * of glass, eta / k of metal, kr of mirror) take any top-level texture in tex[].  Those that are
+ * transformed first (transMatte, shinyMetal, substrate) are either FOLDED -- every input of the
+ * transform was constant, tex[] names a BLING_TEX_CONST record holding the transformed spectrum --
+ * or RAW -- tex[] names the texture as written (any top-level kind, constant included) and the
+ * device applies the transform to its value at the hit:
+ *   transMatte   stex[1] == BLING_SLOT_RAW: tex[0] = kr, tex[1] = kt, both raw (t needs r);
+ *                stex[1] == -1: both folded
+ *   shinyMetal   stex[1] == BLING_SLOT_RAW: tex[0] = tex[1] = ks raw, else both folded;
+ *                stex[2] == BLING_SLOT_RAW: tex[2] = tex[3] = kr raw, else both folded
+ *   substrate    per slot, by the texture's kind: BLING_TEX_CONST = folded, any other kind = raw
+ *                (sClamp 0 1 is idempotent; its stex[0..2] hold the scalar textures)
+ * A material with a scalar texture in stex[0] (other than substrate's) or with a raw slot sets the
+ * feature bit PROCTEX (common/scene_features.h): the path, directLighting, bidir and Metropolis
+ * kernels serve it, the SPPM renderer and the light tracer refuse it. */
+#define BLING_SLOT_RAW 1
 enum bling_mat_kind {
     BLING_MAT_BLACKBODY = 0,   /* blackBodyMaterial: no BxDFs (Reflection.hs:337-338)        */
     BLING_MAT_MATTE = 1,       /* tex[0]=kd, scalar[0]=sigma  -> Lambertian / OrenNayar       */
@@ -109,16 +132,16 @@ enum bling_mat_kind {
     BLING_MAT_GLASS = 3,       /* tex[0]=kr, tex[1]=kt, scalar[0]=ior                         */
     BLING_MAT_METAL = 4,       /* tex[0]=eta, tex[1]=k, scalar[0]=rough                       */
     BLING_MAT_MIRROR = 5,      /* tex[0]=kr                                                   */
-    BLING_MAT_TRANSMATTE = 6,  /* translucentMatte (Material.hs:43-53): tex[0] = sClamp 0 1 kr,
-                                  tex[1] = sClamp 0 1 kt * (white - r) (both folded on the host,
-                                  constant textures only), scalar[0] = ks (sigma)              */
-    BLING_MAT_SHINYMETAL = 7,  /* mkShinyMetal (Material.hs:98-109): conductor spectra folded on
-                                  the host (constant kr / ks only): tex[0] = frApproxEta ks,
+    BLING_MAT_TRANSMATTE = 6,  /* translucentMatte (Material.hs:43-53): tex[0] = r = sClamp 0 1 kr,
+                                  tex[1] = t = sClamp 0 1 kt * (white - r), folded or raw (above),
+                                  scalar[0] = ks (sigma)                                       */
+    BLING_MAT_SHINYMETAL = 7,  /* mkShinyMetal (Material.hs:98-109): conductor spectra, folded or
+                                  raw (above): tex[0] = frApproxEta ks,
                                   tex[1] = frApproxK ks (glossy lobe), tex[2] = frApproxEta kr,
                                   tex[3] = frApproxK kr (specular lobe), scalar[0] = rough     */
     BLING_MAT_SUBSTRATE = 8    /* mkSubstrate (Material.hs:111-128): one FresnelBlend lobe with an
-                                  anisotropic distribution (Microfacet.hs:56-105); constant
-                                  textures folded on the host: tex[0..2] = sClamp 0 1 of kd, ks, ka;
+                                  anisotropic distribution (Microfacet.hs:56-105);
+                                  tex[0..2] = sClamp 0 1 of kd, ks, ka, folded or raw (above);
                                   scalar[0] = fixExponent (1 / max 0 urough), scalar[1] = the same
                                   of vrough, scalar[2] = depth; a non-constant urough / vrough /
                                   depth sets stex[0..2] and is evaluated (and folded) per hit    */
@@ -128,7 +151,8 @@ typedef struct bling_material {
     int32_t kind;
     int32_t tex[4];            /* spectrum texture indices, -1 if unused                     */
     float   scalar[4];         /* constant scalar textures                                    */
-    int32_t stex[4];           /* stex[0..2]: scalar texture replacing scalar[k] at a hit;
+    int32_t stex[4];           /* stex[0..2]: scalar texture replacing scalar[k] at a hit, or the
+                                  raw-slot flags of transMatte / shinyMetal (above);
                                   stex[3]: bumpMap displacement (Reflection.hs:344-377); -1 = none */
 } bling_material;
 
