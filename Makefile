@@ -35,6 +35,7 @@ CORE_HDR := $(wildcard bling_amd/csrc/core/*.h) bling_amd/csrc/common/sky_model.
             bling_amd/csrc/common/spectral_data.h bling_amd/csrc/common/counter_rng.h include/bling.h include/bling_scene.h \
             bling_amd/csrc/common/scene_features.h bling_amd/csrc/common/perlin.h bling_amd/csrc/common/cr_math.h \
             bling_amd/csrc/common/fast_cr.h bling_amd/csrc/common/cellnoise.h bling_amd/csrc/common/image_tex.h
+REF_HDR  := $(wildcard tests/ref/*.h)
 ORA_SRC  := $(wildcard oracle/*.cpp)
 ORA_HDR  := $(wildcard oracle/*.h) include/bling_scene.h bling_amd/csrc/common/perlin.h bling_amd/csrc/common/cr_math.h \
             bling_amd/csrc/common/cellnoise.h bling_amd/csrc/common/image_tex.h
@@ -64,17 +65,17 @@ $(ORADIR)/liboracle.so: $(ORA_SRC) $(ORA_HDR)
 	$(CXX) $(HOSTFLAGS) -fopenmp -shared -o $@ $(ORA_SRC)
 
 # the light tracer's restatement includes oracle/oracle.cpp (its internals are file-local); tests only
-$(LTRDIR)/liblt_ref.so: tests/ref/lighttracer_ref.cpp $(ORA_SRC) $(ORA_HDR)
+$(LTRDIR)/liblt_ref.so: tests/ref/lighttracer_ref.cpp $(REF_HDR) $(ORA_SRC) $(ORA_HDR)
 	@mkdir -p $(LTRDIR)
 	$(CXX) $(HOSTFLAGS) -Wno-subobject-linkage -fopenmp -shared -o $@ tests/ref/lighttracer_ref.cpp
 
 # the bidirectional integrator's restatement, built the same way; tests only
-$(LTRDIR)/libbd_ref.so: tests/ref/bidir_ref.cpp $(ORA_SRC) $(ORA_HDR)
+$(LTRDIR)/libbd_ref.so: tests/ref/bidir_ref.cpp $(REF_HDR) $(ORA_SRC) $(ORA_HDR)
 	@mkdir -p $(LTRDIR)
 	$(CXX) $(HOSTFLAGS) -Wno-subobject-linkage -fopenmp -shared -o $@ tests/ref/bidir_ref.cpp
 
 # the Metropolis renderer's restatement includes the bidirectional one; tests only
-$(LTRDIR)/libmlt_ref.so: tests/ref/mlt_ref.cpp tests/ref/bidir_ref.cpp $(ORA_SRC) $(ORA_HDR) bling_amd/csrc/common/sky_model.h
+$(LTRDIR)/libmlt_ref.so: tests/ref/mlt_ref.cpp tests/ref/bidir_ref.cpp $(REF_HDR) $(ORA_SRC) $(ORA_HDR) bling_amd/csrc/common/sky_model.h
 	@mkdir -p $(LTRDIR)
 	$(CXX) $(HOSTFLAGS) -Wno-subobject-linkage -fopenmp -shared -o $@ tests/ref/mlt_ref.cpp
 

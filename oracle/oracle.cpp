@@ -2610,6 +2610,22 @@ int oracle_bxdf_probe(oracle_scene* os, int mat, int comp, const float* wo3, con
   return bs.n;
 }
 
+// The same component's bxdfSample True wo u, the adjoint branch photons and light subpaths take (wi3
+// is not read): out[0..15] f, [16..18] wi, [19] pdf.  Returns the component count.
+int oracle_bxdf_sample_adj_probe(oracle_scene* os, int mat, int comp, const float* wo3, const float* wi3, const float* u2,
+                                 float* out) {
+  (void)wi3;
+  const bling_scene_desc* d = os->s.d;
+  DG dg = mk_dg(mk(0.f, 0.f, 0.f), 0.5f, 0.5f, mk(1.f, 0.f, 0.f), mk(0.f, 1.f, 0.f));
+  Bsdf bs = make_bsdf(d, mat, dg, dg);
+  if (comp < 0 || comp >= bs.n) return bs.n;
+  V ws; float pdf;
+  S f = bxdf_sample(bs.b[comp], mk(wo3[0], wo3[1], wo3[2]), u2[0], u2[1], &ws, &pdf, true);
+  std::memcpy(out, f.v, 64);
+  out[16] = ws.x; out[17] = ws.y; out[18] = ws.z; out[19] = pdf;
+  return bs.n;
+}
+
 // Light.sample of light `li` seen from world point p (Light.hs:122-160): out = li[16], wi[3], pdf,
 // ray o[3] d[3] tmin tmax (28 floats); Light.pdf p wi (Light.hs:215-229) as the return value of
 // oracle_light_pdf_probe

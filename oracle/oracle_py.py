@@ -81,6 +81,8 @@ def lib() -> C.CDLL:
         L.oracle_tri_probe.restype = C.c_int
         L.oracle_bxdf_probe.argtypes = [C.c_void_p, C.c_int, C.c_int, f32p, f32p, f32p, f32p]
         L.oracle_bxdf_probe.restype = C.c_int
+        L.oracle_bxdf_sample_adj_probe.argtypes = [C.c_void_p, C.c_int, C.c_int, f32p, f32p, f32p, f32p]
+        L.oracle_bxdf_sample_adj_probe.restype = C.c_int
         L.oracle_light_sample_probe.argtypes = [C.c_void_p, C.c_int, f32p, C.c_float, C.c_float, C.c_float, f32p]
         L.oracle_light_pdf_probe.argtypes = [C.c_void_p, C.c_int, f32p, f32p]
         L.oracle_light_pdf_probe.restype = C.c_float

@@ -9,6 +9,8 @@ import subprocess
 
 import numpy as np
 
+import cov_ref
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "ref", "_build", "libbd_ref.so")
@@ -93,6 +95,7 @@ class BidirRef:
         rc = lib().bd_ref_sample_li(self._h, seed, pass_index, s.ctypes.data_as(i32p), n, L.ctypes.data_as(f32p),
                                     terms.ctypes.data_as(f32p), lens.ctypes.data_as(i32p), threads, C.byref(st))
         assert rc == 0
+        self.coverage = cov_ref.read(lib().bd_ref_coverage)     # what this call's light subpaths met
         return L, terms, lens, st
 
     def render(self, seed, pass_index=1, film=None, shard_rank=0, shard_world=1, term_mask=7, threads=0):

@@ -9,6 +9,8 @@ import subprocess
 
 import numpy as np
 
+import cov_ref
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "ref", "_build", "liblt_ref.so")
@@ -72,6 +74,7 @@ class LightRef:
         st = RefStats()
         n = lib().lt_ref_pass(self._h, seed, pass_index, first, count, threads, splat.ctypes.data_as(f32p), None, None,
                               0, C.byref(st))
+        self.coverage = cov_ref.read(lib().lt_ref_coverage)     # what this pass's photons met
         rec = np.zeros(n if records else 0, RECORD)
         self.camz = np.zeros(len(rec), np.float32)      # camera-space z of each record's vertex
         if records and n:

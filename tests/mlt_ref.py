@@ -9,6 +9,8 @@ import subprocess
 
 import numpy as np
 
+import cov_ref
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "ref", "_build", "libmlt_ref.so")
@@ -92,6 +94,7 @@ class MltRef:
         rc = lib().mlt_ref_pass(self._h, seed, pass_index, threads, s64.ctypes.data_as(f64p), s32.ctypes.data_as(f32p),
                                 rec.ctypes.data_as(C.c_void_p), m, starts.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(st),
                                 self.abs64.ctypes.data_as(f64p), self.count.ctypes.data_as(C.POINTER(C.c_uint32)))
+        self.coverage = cov_ref.read(lib().mlt_ref_coverage)    # what this pass's light subpaths met
         if rc == -2:
             raise ValueError("the bootstrap selection reads an unwritten slot")
         if rc != 0:

@@ -12,6 +12,8 @@
 
 #include <algorithm>
 
+#include "coverage.h"
+
 namespace {
 
 // evalBsdf True (Reflection.hs:318-332): eval b = bxdfEval b (not flipped), scaled by |sideTest|
@@ -34,7 +36,7 @@ constexpr int BD_MAX_DEPTH = 16;
 struct Vert { V wi, wo; Hit h; Bsdf bsdf; int type; S alpha; };
 inline bool v_spec(const Vert& v) { return (v.type & B_SPEC) == B_SPEC; }              // bxdfIs Specular
 
-struct BdCount { uint64_t cam = 0, cont = 0, mis = 0, shadow = 0, verts = 0; };
+struct BdCount { uint64_t cam = 0, cont = 0, mis = 0, shadow = 0, verts = 0; Cov cov; };
 
 // sampler dimensions of mkBidirPathIntegrator (:44-48): smps1D * sd * 3 + 1, smps2D * sd * 3 + 2
 SampleCtx bd_sample_ctx(const Scene& Sc, uint32_t seed, uint32_t pass) {
@@ -58,6 +60,7 @@ void next_vertex(bool adj, const Scene& Sc, const SampleCtx& sc, V wi, bool hit,
     rnd2(sc, f2d0 + 9 * depth, &u1, &u2);                                      // :192
     const Bsdf bsdf = hit_bsdf(Sc, h);
     const BsdfSample bs = sample_bsdf_t(bsdf, B_ALL, wi, ubc, u1, u2, adj);    // :194-195
+    if (adj) cov_vertex(C.cov, Sc, h, bsdf, ubc);
     out.push_back(Vert{wi, bs.wi, h, bsdf, bs.flags, alpha});                  // :198
     C.verts++;
     if (is_black(bs.f) || bs.pdf == 0.f) return;                               // :207-208
@@ -112,6 +115,7 @@ S contrib(const Scene& Sc, const SampleCtx& sc, const Ray& r, BdTerms* T, BdCoun
   std::vector<Vert> lp, ep;
   {                                                                            // lightPath (:167-173)
     const LightRay lr = sample_light_ray(Sc, ul, uo1, uo2, ud1, ud2);
+    cov_light_ray(C.cov, Sc, ul);
     const V wo = -lr.ray.d;                                                    // not normalised, pdf not tested
     const S li = sscale(lr.li, absdot(lr.n, wo) / lr.pdf);
     Hit h;
@@ -181,6 +185,10 @@ extern "C" {
 
 struct bd_ref_stats { uint64_t samples, rays_camera, rays_continuation, rays_mis, rays_shadow, path_vertices, dropped; double seconds; };
 
+// what the light subpaths of the last bd_ref_sample_li / bd_ref_render met (coverage.h)
+static Cov g_bd_cov;
+void bd_ref_coverage(uint64_t* out) { std::memcpy(out, g_bd_cov.c, sizeof g_bd_cov.c); }
+
 static void bd_add(bd_ref_stats* st, const BdCount& C) {
   st->rays_camera += C.cam; st->rays_continuation += C.cont; st->rays_mis += C.mis; st->rays_shadow += C.shadow;
   st->path_vertices += C.verts;
@@ -210,6 +218,8 @@ int bd_ref_sample_li(const oracle_scene* os, uint32_t seed, uint32_t pass, const
     }
     if (lens) { lens[4 * i] = T.ne; lens[4 * i + 1] = T.nl; lens[4 * i + 2] = (int)T.emask; lens[4 * i + 3] = (int)T.lmask; }
   }
+  g_bd_cov = Cov{};
+  for (size_t i = 0; i < n; ++i) g_bd_cov.add(cnt[i].cov);
   if (st) {
     for (size_t i = 0; i < n; ++i) bd_add(st, cnt[i]);
     st->samples += n;
@@ -270,6 +280,8 @@ int bd_ref_render(const oracle_scene* os, uint32_t seed, uint32_t pass, int shar
         for (int c = 0; c < 4; ++c) o[c] = o[c] + q[c];
       }
   }
+  g_bd_cov = Cov{};
+  for (size_t i = 0; i < todo.size(); ++i) g_bd_cov.add(cs[i].cov);
   if (st) {
     for (size_t i = 0; i < todo.size(); ++i) { bd_add(st, cs[i]); st->samples += smp[i]; st->dropped += drp[i]; }
     st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

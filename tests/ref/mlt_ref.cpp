@@ -160,6 +160,10 @@ struct mlt_ref_stats {
   double seconds;
 };
 
+// what the light subpaths of the last mlt_ref_pass met, bootstrap and chain evaluations together (coverage.h)
+static Cov g_mlt_cov;
+void mlt_ref_coverage(uint64_t* out) { std::memcpy(out, g_mlt_cov.c, sizeof g_mlt_cov.c); }
+
 // One pass with the scene's metropolis block: splat64 / splat32 (W * H * 3, accumulated in (chain,
 // mutation, current-then-proposal) order; may be NULL), the records of every chain sorted by (chain,
 // mutation) (rec of cap entries, may be NULL; the count is M), starts (chains entries, may be NULL),
@@ -225,7 +229,7 @@ int mlt_ref_pass(const oracle_scene* os, uint32_t seed, uint32_t pass, int threa
   }
   mlt_ref_stats T{};
   BdCount cnt;
-  auto add = [&](const BdCount& x) { cnt.cam += x.cam; cnt.cont += x.cont; cnt.mis += x.mis; cnt.shadow += x.shadow; cnt.verts += x.verts; };
+  auto add = [&](const BdCount& x) { cnt.cam += x.cam; cnt.cont += x.cont; cnt.mis += x.mis; cnt.shadow += x.shadow; cnt.verts += x.verts; cnt.cov.add(x.cov); };
   for (int i = 0; i < nboot; ++i) add(bc[i]);
   for (uint64_t c = 0; c < C; ++c) {
     add(out[c].cnt);
@@ -239,6 +243,7 @@ int mlt_ref_pass(const oracle_scene* os, uint32_t seed, uint32_t pass, int threa
     }
     if (starts) starts[c] = (uint32_t)start[c];
   }
+  g_mlt_cov = cnt.cov;
   if (st) {
     T.b = b; T.mutations = M;
     T.rays_camera = cnt.cam; T.rays_continuation = cnt.cont; T.rays_mis = cnt.mis; T.rays_shadow = cnt.shadow;
