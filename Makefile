@@ -9,6 +9,7 @@
 #   tests/ref/_build/liblt_ref.so     CPU restatement of the light tracer over the oracle (tests)
 #   tests/ref/_build/libbd_ref.so     CPU restatement of the bidirectional integrator over the oracle (tests)
 #   tests/ref/_build/libmlt_ref.so    CPU restatement of the Metropolis renderer over that one (tests)
+#   tests/ref/_build/libnm_ref.so     CPU restatement of the normal-map integrator over the oracle (tests)
 
 HIPCC    ?= /opt/rocm/bin/hipcc
 CXX      ?= g++
@@ -47,7 +48,7 @@ HIPFLAGS  := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -ffp-contract=off -fno-
 
 all: $(LIBDIR)/libbling_host.so $(LIBDIR)/libbling_hip.so $(ORADIR)/liboracle.so $(LIBDIR)/bling \
      $(LIBDIR)/libbling_mathcheck.so $(LTRDIR)/liblt_ref.so $(LTRDIR)/libbd_ref.so \
-     $(LTRDIR)/libmlt_ref.so
+     $(LTRDIR)/libmlt_ref.so $(LTRDIR)/libnm_ref.so
 
 host: $(LIBDIR)/libbling_host.so
 oracle: $(ORADIR)/liboracle.so
@@ -55,6 +56,7 @@ core: $(LIBDIR)/libbling_hip.so
 ltref: $(LTRDIR)/liblt_ref.so
 bdref: $(LTRDIR)/libbd_ref.so
 mltref: $(LTRDIR)/libmlt_ref.so
+nmref: $(LTRDIR)/libnm_ref.so
 
 $(LIBDIR)/libbling_host.so: $(HOST_SRC) $(HOST_HDR)
 	@mkdir -p $(LIBDIR)
@@ -79,6 +81,11 @@ $(LTRDIR)/libmlt_ref.so: tests/ref/mlt_ref.cpp tests/ref/bidir_ref.cpp $(REF_HDR
 	@mkdir -p $(LTRDIR)
 	$(CXX) $(HOSTFLAGS) -Wno-subobject-linkage -fopenmp -shared -o $@ tests/ref/mlt_ref.cpp
 
+# the normal-map integrator's restatement, built like the light tracer's; tests only
+$(LTRDIR)/libnm_ref.so: tests/ref/normals_ref.cpp $(ORA_SRC) $(ORA_HDR)
+	@mkdir -p $(LTRDIR)
+	$(CXX) $(HOSTFLAGS) -Wno-subobject-linkage -fopenmp -shared -o $@ tests/ref/normals_ref.cpp
+
 # one object per unit (core, sppm driver, one per kernel feature profile) so make -j compiles the
 # kernel instantiations in parallel
 $(OBJDIR)/%.o: bling_amd/csrc/core/% $(CORE_HDR)
@@ -89,6 +96,8 @@ $(OBJDIR)/%.o: bling_amd/csrc/core/% $(CORE_HDR)
 $(OBJDIR)/bidir_pass_walk.hip.o $(OBJDIR)/bidir_pass_connect.hip.o: bling_amd/csrc/core/bidir_pass.hip
 # and so does the Metropolis walk unit
 $(OBJDIR)/mlt_pass_walk.hip.o: bling_amd/csrc/core/mlt_pass.hip
+# the normal-map units of the larger profiles include the driver unit's source
+$(OBJDIR)/normals_pass_b.hip.o $(OBJDIR)/normals_pass_c.hip.o: bling_amd/csrc/core/normals_pass.hip
 
 $(LIBDIR)/libbling_hip.so: $(CORE_OBJ)
 	@mkdir -p $(LIBDIR)
@@ -113,4 +122,4 @@ variant: $(CORE_OBJ)
 clean:
 	rm -rf $(LIBDIR) $(ORADIR) $(LTRDIR) build
 
-.PHONY: all host oracle core ltref bdref mltref clean variant
+.PHONY: all host oracle core ltref bdref mltref nmref clean variant

@@ -120,7 +120,7 @@ void validate_scene(const bling_scene_desc* d) {
     if (d->config.max_depth < 1 || d->config.max_depth > BD_MAX_DEPTH)
       throw std::invalid_argument("bidir maxDepth outside [1, " + std::to_string(BD_MAX_DEPTH) + "]");
     if (d->config.sample_depth < 0) throw std::invalid_argument("bidir sampleDepth < 0");
-  } else if (d->config.integrator != BLING_INTEGRATOR_PATH) {
+  } else if (d->config.integrator != BLING_INTEGRATOR_PATH && d->config.integrator != BLING_INTEGRATOR_NORMALS) {
     throw std::invalid_argument("unknown surface integrator");
   }
   for (uint32_t k = 0; k < d->num_textures; ++k) {     // computed textures: children the device resolves
@@ -503,6 +503,7 @@ void upload_scene(bling_ctx* c, const bling_scene_desc* d) {
   }
   if (S.integrator == BLING_INTEGRATOR_DIRECT) S.n1d = S.n2d = 2 * cfg.max_depth;   // DirectLighting.hs:17-18
   else if (S.integrator == BLING_INTEGRATOR_BIDIR) { S.n1d = 12 * S.sample_depth + 1; S.n2d = 9 * S.sample_depth + 2; }   // BidirPath.hs:44-48
+  else if (S.integrator == BLING_INTEGRATOR_NORMALS) { S.n1d = S.n2d = 0; S.max_depth = S.sample_depth = 0; }   // SurfaceIntegrator li 0 0 (Debug.hs:26)
   else { S.n1d = 4 * cfg.sample_depth; S.n2d = 3 * cfg.sample_depth; }              // Path.hs:26-28
   if (cfg.spp > (1 << 24)) throw std::runtime_error("more than 2^24 samples per pixel (the sampler's permutation, counter_rng.h)");
   S.fd_spp = FastDiv::make((uint32_t)std::max(1, cfg.spp));
@@ -758,7 +759,8 @@ int render(bling_ctx* c, const bling_pass_params* p, float* film_dev, bling_stat
       k_reset_queues<<<1, 64, 0, s>>>(P.qcount, off);
       k_raygen<<<g, 256, 0, s>>>(c->dscene.p, P, c->tiles_dev.p, p->seed, p->pass_index);
       HIPCHK(hipEventRecord(eb0, s));
-      launches += (uint64_t)run_wave(c, P, off, p->seed, p->pass_index, stats_on, &tm);
+      if (S.integrator == BLING_INTEGRATOR_NORMALS) launches += (uint64_t)normals_wave(c, P, off, &tm);
+      else launches += (uint64_t)run_wave(c, P, off, p->seed, p->pass_index, stats_on, &tm);
     }
     HIPCHK(hipEventRecord(eb1, s));
     launch_film(c, P, c->tiles_dev.p, (unsigned)batch.size(), film_dev, timg ? timg + t0 * slot_floats : nullptr);
@@ -1099,7 +1101,8 @@ static int sample_li_impl(bling_ctx* c, uint32_t seed, uint32_t pass_index, cons
       unsigned blocks = (unsigned)((n + 255) / 256);
       k_reset_queues<<<1, 64, 0, s>>>(P.qcount, (uint32_t)n);
       k_raygen_list<<<blocks, 256, 0, s>>>(c->dscene.p, P, list.p, (uint32_t)n, seed, pass_index);
-      run_wave(c, P, (uint32_t)n, seed, pass_index, false);
+      if (S.integrator == BLING_INTEGRATOR_NORMALS) normals_wave(c, P, (uint32_t)n, nullptr);
+      else run_wave(c, P, (uint32_t)n, seed, pass_index, false);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
@@ -1119,7 +1122,7 @@ static int sample_li_impl(bling_ctx* c, uint32_t seed, uint32_t pass_index, cons
       st->camera_samples = n;
       st->rays_camera = hc.cam; st->rays_continuation = hc.cont; st->rays_mis = hc.mis; st->rays_shadow = hc.shadow;
       st->dropped_samples = hc.dropped;
-      if (S.integrator == BLING_INTEGRATOR_BIDIR) st->path_vertices = hc.vertices;
+      if (S.integrator == BLING_INTEGRATOR_BIDIR || S.integrator == BLING_INTEGRATOR_NORMALS) st->path_vertices = hc.vertices;
     }
     return BLING_OK;
   });

@@ -63,6 +63,7 @@ struct DBuf {
 // pipeline, plus result, img, six queue words and the queue flag
 constexpr uint64_t kSetBytes = 8 * 16 + 8 + 3 * 4 + 64 + 64;
 constexpr uint64_t kSetSpectraBytes = 3 * 64;
+constexpr uint64_t kLeanSetBytes = 4 * 16;   // the normal-map integrator's set: org, dir, hit, meta
 constexpr uint64_t kPathFixedBytes = 16 + 8 + 6 * 4 + 1 + 4 + 2 * 4;   // ... + the k_march results (2 words)
 // DirectLighting adds the continuation origin, the sibling mask and one parked ray (org, dir,
 // weight) per level below maxDepth
@@ -187,7 +188,15 @@ struct bling_ctx {
     DBuf<float2> mhit;
     DBuf<float> fm;
     DBuf<uint32_t> occ, rtex;
-    void alloc(uint32_t n, bool spectra) {
+    // lean: the records the camera rays, one closest-hit launch and the film need (org, dir, hit,
+    // meta) and nothing else -- the normal-map integrator's set (normals.h)
+    void alloc(uint32_t n, bool spectra, bool lean = false) {
+      if (lean) {
+        free();
+        for (auto* b : {&org, &dir, &hit}) b->alloc(n);
+        meta.alloc(n);
+        return;
+      }
       for (auto* b : {&org, &dir, &hit, &mdir, &fac, &sh_o, &sh_d}) b->alloc(n);
       meta.alloc(n); mhit.alloc(n); fm.alloc(n); occ.alloc(n); rtex.alloc(n);
       T.alloc((size_t)4 * n); L.alloc((size_t)4 * n);
@@ -203,7 +212,7 @@ struct bling_ctx {
                      T.p, Tn.p, L.p, lsc.p, bsc.p};
     }
   } set[2];
-  bool sets_spectra = false, sets_two = false;     // layout of the allocated sets
+  bool sets_spectra = false, sets_two = false, sets_lean = false;   // layout of the allocated sets
   DBuf<float4> corg, dl_org, dl_dir, dl_T;          // DirectLighting only
   DBuf<uint32_t> dl_mask;
   int dl_levels = 0;                                // slots allocated per path (0 = Path)
@@ -267,8 +276,9 @@ struct bling_ctx {
   bool want_spectra() const;
   bool want_two_sets() const { return S.integrator == BLING_INTEGRATOR_PATH; }
   int want_bd_depth() const { return S.integrator == BLING_INTEGRATOR_BIDIR ? S.max_depth : 0; }
+  bool want_lean() const { return S.integrator == BLING_INTEGRATOR_NORMALS; }
   uint64_t path_bytes() const {
-    const uint64_t set_b = kSetBytes + (want_spectra() ? kSetSpectraBytes : 0);
+    const uint64_t set_b = want_lean() ? kLeanSetBytes : kSetBytes + (want_spectra() ? kSetSpectraBytes : 0);
     return (want_two_sets() ? 2 : 1) * set_b + kPathFixedBytes + (want_dl_levels() ? 20 + kDlSlotBytes * want_dl_levels() : 0) +
            (want_bd_depth() ? bd_sample_bytes(want_bd_depth()) : 0);
   }
@@ -284,11 +294,12 @@ struct bling_ctx {
     } else if (bidir.cap) {
       bidir.free_all();
     }
-    const bool relayout = lv != dl_levels || sp != sets_spectra || two != sets_two;
+    const bool lean = want_lean();
+    const bool relayout = lv != dl_levels || sp != sets_spectra || two != sets_two || lean != sets_lean;
     if (n <= cap && !relayout) return;
     cap = std::max(cap, (n + 255u) & ~255u);
-    dl_levels = lv; sets_spectra = sp; sets_two = two;
-    set[0].alloc(cap, sp);
+    dl_levels = lv; sets_spectra = sp; sets_two = two; sets_lean = lean;
+    set[0].alloc(cap, sp, lean);
     if (two) set[1].alloc(cap, sp); else set[1].free();
     if (lv) {
       corg.alloc(cap); dl_mask.alloc(cap);
@@ -438,6 +449,7 @@ inline bool bling_ctx::want_spectra() const {
   bool full = true;
   bcore::with_profile(features, [&](auto prof) { full = !bd::factored<decltype(prof)::value>(); });
   if (S.integrator == BLING_INTEGRATOR_BIDIR) return false;   // its kernels keep no path set (bidir.h)
+  if (S.integrator == BLING_INTEGRATOR_NORMALS) return false; // one closest hit per sample, no spectra (normals.h)
   return full || S.integrator == BLING_INTEGRATOR_DIRECT;
 }
 
@@ -508,5 +520,10 @@ uint32_t light_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, uint32_t first
 // textures included: a vertex's BSDF is rebuilt where it is used).  Returns the launches.
 int bidir_wave(bling_ctx* c, const WaveState& W, const TileDesc* tiles, unsigned n_tiles, uint32_t max_tile,
                const int32_t* list, uint32_t n, uint32_t seed, uint32_t pass, float* terms);
+// One wave of the normal-map integrator (normals_pass.hip): the n camera samples k_raygen / k_raygen_list
+// left in W (slot = sample id, the closest queue holding them all), traced with the scene's planned
+// closest-hit launch and shaded by k_shade_nm into W.result (and W.Lfull).  tm (may be NULL): event
+// pairs around the two launches of a timed pass.  Returns the launches.
+int normals_wave(bling_ctx* c, const WaveState& W, uint32_t n, WaveTiming* tm);
 
 }  // namespace bcore

@@ -266,6 +266,7 @@ struct Overrides {
   bool path = false; int md = 0, sd = 0;
   bool direct = false; int dmd = 0;
   bool bidir = false; int bmd = 0, bsd = 0;
+  bool normals = false;
   bool force_path = false;
   bool filter = false; int fkind = 0; float fp[5] = {0, 0, 0, 0, 0};
   bool sppm = false; int sp_photons = 0, sp_md = 0; float sp_radius = 0.f, sp_alpha = 0.8f;
@@ -1198,7 +1199,13 @@ struct Parser {
             } else if (it == "bidir") {                                       // IntegratorParser.hs:19-22
               B.cfg.max_depth = named_int("maxDepth"); B.cfg.sample_depth = named_int("sampleDepth");
               B.cfg.renderer = BLING_RENDERER_SAMPLER_PATH; B.cfg.integrator = BLING_INTEGRATOR_BIDIR;
+            } else if (it == "debug" && L.is_word("normals")) {               // IntegratorParser.hs:29-35, mkNormalMap
+              L.word();
+              B.cfg.max_depth = 0; B.cfg.sample_depth = 0;
+              B.cfg.renderer = BLING_RENDERER_SAMPLER_PATH; B.cfg.integrator = BLING_INTEGRATOR_NORMALS;
             }
+            // debug kdtree / debug reference are `undefined` in the reference (Debug.hs:23,37) and any other
+            // word after `debug` fails its parser: not served
             // bidirnod reaches `undefined` in the reference (BidirPath.hs:66): not served, like the rest
             else { B.cfg.renderer = BLING_RENDERER_OTHER; while (L.peekc() != '}') { if (L.peek_number()) L.flt(); else L.word(); } }
           });
@@ -1304,6 +1311,7 @@ Overrides parse_overrides(const char* s) {
     else if (k == "path") { o.path = true; o.md = I(0); o.sd = I(1); }
     else if (k == "direct") { o.direct = true; o.dmd = I(0); }
     else if (k == "bidir") { o.bidir = true; o.bmd = I(0); o.bsd = I(1); }
+    else if (k == "normals") { o.normals = true; }      // integrator { debug normals }: no arguments
     else if (k == "force_path") { o.force_path = I(0) != 0; }
     else if (k == "sppm") {                             // sppm=photonCount,maxDepth,radius[,alpha]
       o.sppm = true; o.sp_photons = I(0); o.sp_md = I(1); o.sp_radius = Fv(2);
@@ -1357,12 +1365,13 @@ int bling_host_load(const char* path, const char* overrides, bling_host_scene** 
     P.job();
     // renderer overrides (trap T1: the last `renderer` block wins; the harness forces path)
     // force_path selects the sampler renderer and keeps a parsed surface integrator; path= / direct= /
-    // bidir= also replace the integrator
-    if (B.ov.force_path || B.ov.path || B.ov.direct || B.ov.bidir || B.ov.strat || B.ov.random) {
-      if (B.ov.force_path || B.ov.path || B.ov.direct || B.ov.bidir) B.cfg.renderer = BLING_RENDERER_SAMPLER_PATH;
+    // bidir= / normals also replace the integrator
+    if (B.ov.force_path || B.ov.path || B.ov.direct || B.ov.bidir || B.ov.normals || B.ov.strat || B.ov.random) {
+      if (B.ov.force_path || B.ov.path || B.ov.direct || B.ov.bidir || B.ov.normals) B.cfg.renderer = BLING_RENDERER_SAMPLER_PATH;
       if (B.ov.path) { B.cfg.max_depth = B.ov.md; B.cfg.sample_depth = B.ov.sd; B.cfg.integrator = BLING_INTEGRATOR_PATH; }
       if (B.ov.direct) { B.cfg.max_depth = B.ov.dmd; B.cfg.sample_depth = 0; B.cfg.integrator = BLING_INTEGRATOR_DIRECT; }
       if (B.ov.bidir) { B.cfg.max_depth = B.ov.bmd; B.cfg.sample_depth = B.ov.bsd; B.cfg.integrator = BLING_INTEGRATOR_BIDIR; }
+      if (B.ov.normals) { B.cfg.max_depth = 0; B.cfg.sample_depth = 0; B.cfg.integrator = BLING_INTEGRATOR_NORMALS; }
       if (B.ov.strat) { B.cfg.sampler = BLING_SAMPLER_STRATIFIED; B.cfg.nu = B.ov.nu; B.cfg.nv = B.ov.nv; B.cfg.spp = B.ov.nu * B.ov.nv; }
       if (B.ov.random) { B.cfg.sampler = BLING_SAMPLER_RANDOM; B.cfg.spp = B.ov.spp; }
     }
@@ -1454,7 +1463,7 @@ int bling_host_load(const char* path, const char* overrides, bling_host_scene** 
     sm << "image " << B.resX << "x" << B.resY << ", prims " << d.num_prims << " (triangles "
        << d.num_triangles << ", shapes " << d.num_shapes << ", fractal " << d.fractal.present << "), lights "
        << d.num_lights << ", materials " << d.num_materials << ", renderer "
-       << (B.cfg.renderer == BLING_RENDERER_LIGHT ? "light" : B.cfg.renderer == BLING_RENDERER_METROPOLIS ? "metropolis" : B.cfg.renderer != BLING_RENDERER_SAMPLER_PATH ? "other" : B.cfg.integrator == BLING_INTEGRATOR_DIRECT ? "direct" : B.cfg.integrator == BLING_INTEGRATOR_BIDIR ? "bidir" : "path")
+       << (B.cfg.renderer == BLING_RENDERER_LIGHT ? "light" : B.cfg.renderer == BLING_RENDERER_METROPOLIS ? "metropolis" : B.cfg.renderer != BLING_RENDERER_SAMPLER_PATH ? "other" : B.cfg.integrator == BLING_INTEGRATOR_DIRECT ? "direct" : B.cfg.integrator == BLING_INTEGRATOR_BIDIR ? "bidir" : B.cfg.integrator == BLING_INTEGRATOR_NORMALS ? "normals" : "path")
        << " md=" << B.cfg.max_depth
        << " sd=" << B.cfg.sample_depth << " sampler "
        << (B.cfg.sampler == BLING_SAMPLER_STRATIFIED ? "stratified " : "random ") << B.cfg.nu << "x"

@@ -93,6 +93,24 @@ MLT_SCENES = {
 }
 
 
+# The normal-map integrator (`integrator { debug normals }`, override normals) on scenes of this
+# repository, for its parity tests (tests/test_normals.py, tests/test_gpu_normals.py): every way a
+# shading normal is made and every closest-hit plan.
+NORMAL_SCENES = {
+    "N1": BenchConfig("N1", "cornell-box.bling", "image=48,48;stratified=2,2;normals", 0),     # triangles, BVH4 all-LDS
+    "N2": BenchConfig("N2", "normals.bling", "", 0),                                           # smooth mesh, bump, mirrored shape
+    "N3": BenchConfig("N3", "shapes-materials.bling", "normals", 0),                           # disk / cylinder / box / sphere / quad
+    "N4": BenchConfig("N4", "bumpmap.bling", "image=64,36;stratified=2,2;normals", 0),         # fBm bump, sun-sky behind it
+    "N5": BenchConfig("N5", "heightmap-sinc.bling", "normals", 0),                             # heightMap shading normals, sinc 4 film
+    "N6": BenchConfig("N6", "bezier.bling", "normals", 0),                                     # Bezier tessellation's normals
+    "N7": BenchConfig("N7", "ducky.bling", "image=48,48;normals", 0),                          # 13 k triangles: LDS prefix + global fallback
+    "N8": BenchConfig("N8", "mandelbulb.bling", "image=16,16;stratified=2,2;normals", 0),      # the pre-marched fractal's gradient
+    "N9": BenchConfig("N9", "julia.bling", "image=24,18;normals", 0),                          # the Julia normal
+    "N10": BenchConfig("N10", "sun-sky.bling", "image=48,27;random=4;normals", 0),             # escaped rays stay black under the sky
+    "N11": BenchConfig("N11", "envmap.bling", "image=48,24;random=4;normals", 0),              # camera { environment }
+}
+
+
 class Job:
     """A parsed `.bling` job: RenderJob + the sampler/path renderer configuration."""
 
@@ -203,7 +221,8 @@ def parse_job(path: str, overrides: str | None = None) -> Job:
 
 
 def load_config(name: str, overrides_extra: str | None = None) -> Job:
-    c = CONFIGS[name] if name in CONFIGS else BIDIR_SCENES[name] if name in BIDIR_SCENES else MLT_SCENES[name] if name in MLT_SCENES else FEATURE_SCENES[name]
+    c = (CONFIGS[name] if name in CONFIGS else BIDIR_SCENES[name] if name in BIDIR_SCENES else MLT_SCENES[name] if name in MLT_SCENES
+         else NORMAL_SCENES[name] if name in NORMAL_SCENES else FEATURE_SCENES[name])
     ov = ";".join(x for x in (c.overrides, overrides_extra) if x)
     return Job(c.path, ov or None)
 

@@ -136,9 +136,12 @@ int bling_scene_upload(bling_ctx* ctx, const bling_scene_desc* desc);
 int bling_scene_validate(const bling_scene_desc* desc);
 
 /* Replaces: prender's onePass (Rendering.hs:127-140) for the `sampler` renderer with its `path`
- * (Integrator/Path.hs), `directLighting` (Integrator/DirectLighting.hs) or `bidir`
- * (Integrator/BidirPath.hs) surface integrator, selected by desc->config.integrator at upload
- * (directLighting and bidir maxDepth must lie in [1, 16]; else BLING_EINVAL with the reason).  A bidir
+ * (Integrator/Path.hs), `directLighting` (Integrator/DirectLighting.hs), `bidir`
+ * (Integrator/BidirPath.hs) or `debug normals` (Integrator/Debug.hs:25-34) surface integrator, selected
+ * by desc->config.integrator at upload
+ * (directLighting and bidir maxDepth must lie in [1, 16]; else BLING_EINVAL with the reason).  A normal-map
+ * pass traces the camera rays once and adds rgbToSpectrumRefl ((1 + n) / 2) of the hit's shading normal
+ * (black on a miss, no environment term); BLING_PASS_TRAVERSAL_STATS leaves its traversal counters at 0.  A bidir
  * pass keeps 2 maxDepth vertex records per sample in flight and is cut into more waves accordingly;
  * its ray counts are mapped as bling_sample_li describes.
  * film_out: host buffer of width*height*4 floats (W, X, Y, Z per pixel, Image.hs:64-71),
@@ -224,7 +227,8 @@ int bling_trace_device(bling_ctx* ctx, const void* rays_soa_dev, size_t n, int a
  * for the bidirectional integrator: rays_camera = camera samples traced, rays_continuation = the
  * closest-hit queries of both subpaths' segments (the light ray included), rays_mis = estimateDirect's
  * BSDF-MIS rays, rays_shadow = its shadow rays plus the connections' occluded queries,
- * path_vertices = the vertices of both subpaths. */
+ * path_vertices = the vertices of both subpaths; for the normal-map integrator: rays_camera = the
+ * samples, path_vertices = the samples whose camera ray hit, every other ray count 0. */
 int bling_sample_li(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, const int32_t* samples, size_t n,
                     float* L_out, float* img_out, bling_stats* stats);
 

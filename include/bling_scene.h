@@ -271,7 +271,9 @@ enum bling_renderer_kind {
 enum bling_integrator_kind {
     BLING_INTEGRATOR_PATH = 0,     /* path maxDepth sampleDepth        (Integrator/Path.hs)           */
     BLING_INTEGRATOR_DIRECT = 1,   /* directLighting maxDepth          (Integrator/DirectLighting.hs) */
-    BLING_INTEGRATOR_BIDIR = 2     /* bidir maxDepth sampleDepth       (Integrator/BidirPath.hs)      */
+    BLING_INTEGRATOR_BIDIR = 2,    /* bidir maxDepth sampleDepth       (Integrator/BidirPath.hs)      */
+    BLING_INTEGRATOR_NORMALS = 3   /* debug normals: the shading normal as a colour, no sample dimensions,
+                                      maxDepth = sampleDepth = 0       (Integrator/Debug.hs:25-34)    */
 };
 
 typedef struct bling_render_config {
