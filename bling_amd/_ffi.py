@@ -107,6 +107,14 @@ class MltRecord(C.Structure):
                 ("i_prop", C.c_float), ("a", C.c_float), ("flags", C.c_uint32), ("pad", C.c_uint32)]
 
 
+DEVELOP_RGB_F32, DEVELOP_RGB8, DEVELOP_RGBE = 0, 1, 2   # BLING_DEVELOP_*
+
+
+class DevelopParams(C.Structure):
+    """bling_develop_params (include/bling.h); window = x0, x1, y0, y1, inclusive."""
+    _fields_ = [("format", C.c_int32), ("splat_weight", C.c_float), ("window", C.c_int32 * 4)]
+
+
 class RenderConfig(C.Structure):
     _fields_ = [("renderer", C.c_int32), ("sampler", C.c_int32), ("nu", C.c_int32), ("nv", C.c_int32),
                 ("spp", C.c_int32), ("max_depth", C.c_int32), ("sample_depth", C.c_int32),
@@ -144,6 +152,16 @@ def host() -> C.CDLL:
         lib.bling_host_rgb_pixels.argtypes = [c_f32p, C.c_int, C.c_int, C.POINTER(C.c_uint8)]
         lib.bling_host_write_png.argtypes = [C.c_char_p, c_f32p, C.c_int, C.c_int]
         lib.bling_host_write_png.restype = C.c_int
+        c_u8p = C.POINTER(C.c_uint8)
+        lib.bling_host_rgb_pixels_splat.argtypes = [c_f32p, c_f32p, C.c_float, C.c_int, C.c_int, c_u8p]
+        lib.bling_host_write_png_splat.argtypes = [C.c_char_p, c_f32p, c_f32p, C.c_float, C.c_int, C.c_int]
+        lib.bling_host_write_png_splat.restype = C.c_int
+        lib.bling_host_gamma_thresholds.argtypes = [c_f32p]
+        lib.bling_host_gamma_thresholds.restype = None
+        lib.bling_host_write_png_rgb8.argtypes = [C.c_char_p, c_u8p, C.c_int, C.c_int]
+        lib.bling_host_write_png_rgb8.restype = C.c_int
+        lib.bling_host_write_hdr_rgbe.argtypes = [C.c_char_p, c_u8p, C.c_int, C.c_int]
+        lib.bling_host_write_hdr_rgbe.restype = C.c_int
         _host = lib
     return _host
 
@@ -152,7 +170,7 @@ HIP_SYMBOLS = ["bling_create", "bling_scene_upload", "bling_scene_validate", "bl
                "bling_trace", "bling_trace_device", "bling_sample_li", "bling_sample_li_vertices", "bling_pass_tile_layout",
                "bling_film_add_tiles", "bling_film_add_shards", "bling_sppm_pass", "bling_sppm_pixel_stats", "bling_sppm_reset",
                "bling_render", "bling_debug_stream_bytes", "bling_debug_scene_info", "bling_debug_mis_culled", "bling_debug_set_mis_cull", "bling_debug_set_pipeline", "bling_debug_pass_results", "bling_debug_compact", "bling_debug_sppm_hitpoints", "bling_debug_sppm_buckets",
-               "bling_light_pass", "bling_debug_light_records", "bling_mlt_pass", "bling_debug_mlt_records", "bling_debug_mlt_boot", "bling_debug_mlt_set_boot", "bling_debug_bidir_terms", "bling_destroy", "bling_last_error", "bling_version"]
+               "bling_film_develop", "bling_film_develop_device", "bling_light_pass", "bling_debug_light_records", "bling_mlt_pass", "bling_debug_mlt_records", "bling_debug_mlt_boot", "bling_debug_mlt_set_boot", "bling_debug_bidir_terms", "bling_destroy", "bling_last_error", "bling_version"]
 
 
 class Progress(C.Structure):
@@ -235,6 +253,11 @@ def hip() -> C.CDLL:
             lib.bling_debug_bidir_terms.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.c_size_t,
                                                     c_f32p, C.POINTER(C.c_int32)]
             lib.bling_debug_bidir_terms.restype = C.c_int
+        if hasattr(lib, "bling_film_develop"):        # older experiment builds lack the develop entry points
+            lib.bling_film_develop_device.argtypes = [C.c_void_p, C.POINTER(DevelopParams), C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.bling_film_develop_device.restype = C.c_int
+            lib.bling_film_develop.argtypes = [C.c_void_p, C.POINTER(DevelopParams), c_f32p, c_f32p, C.c_void_p]
+            lib.bling_film_develop.restype = C.c_int
         lib.bling_debug_scene_info.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
         lib.bling_debug_scene_info.restype = C.c_int
         if hasattr(lib, "bling_debug_mis_culled"):    # older experiment builds lack it

@@ -994,6 +994,7 @@ int bling_create(const int* device_ids, int n_devices, bling_ctx** out) {
       return x;
     };
     auto c = make(ids[0]);
+    develop_table(c.get());   // rgbPixels' thresholds (bling_film_develop runs on the first device only)
     // further devices: peer contexts of the fan-out (render_fanout); the primary reads their films
     // over xGMI, so peer access is enabled where the pair supports it (a repeated id -- test hook
     // only -- runs two contexts on one device)
@@ -1186,6 +1187,60 @@ int bling_film_add_shards(bling_ctx* c, const bling_pass_params* p, const void* 
     }
     add_tiles(c, sets, static_cast<float*>(film_device));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return BLING_OK;
+  });
+}
+
+namespace {
+// the checks the two develop calls share; BLING_OK, or the error with g_err set
+int develop_check(bling_ctx* c, const bling_develop_params* dp, const void* film, const void* out) {
+  if (!c || !dp || !film || !out) throw std::invalid_argument("null argument");
+  if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
+  if (dp->format != BLING_DEVELOP_RGB_F32 && dp->format != BLING_DEVELOP_RGB8 && dp->format != BLING_DEVELOP_RGBE)
+    throw std::invalid_argument("develop: unknown format " + std::to_string(dp->format));
+  return BLING_OK;
+}
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa < pb + nb && pb < pa + na;
+}
+}  // namespace
+
+int bling_film_develop_device(bling_ctx* c, const bling_develop_params* dp, const void* film, const void* splat, void* out) {
+  return guarded([&] {
+    if (int rc = develop_check(c, dp, film, out)) return rc;
+    const size_t px = (size_t)c->S.width * c->S.height, nout = px * develop_pixel_bytes(dp->format);
+    if (ranges_overlap(out, nout, film, px * 16) || (splat && ranges_overlap(out, nout, splat, px * 12)))
+      throw std::invalid_argument("develop: out overlaps the film or the splat buffer");
+    HIPCHK(hipSetDevice(c->device));
+    develop_launch(c, dp, static_cast<const float*>(film), static_cast<const float*>(splat), out);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return BLING_OK;
+  });
+}
+
+int bling_film_develop(bling_ctx* c, const bling_develop_params* dp, const float* film, const float* splat, void* out) {
+  return guarded([&] {
+    if (int rc = develop_check(c, dp, film, out)) return rc;
+    int x0, x1, y0, y1;
+    if (!develop_clip(c, dp->window, &x0, &x1, &y0, &y1)) return (int)BLING_OK;   // nothing to write
+    HIPCHK(hipSetDevice(c->device));
+    const size_t w = (size_t)c->S.width, px = w * c->S.height, bpp = develop_pixel_bytes(dp->format);
+    if (c->film_dev.n != px * 4) c->film_dev.alloc(px * 4);
+    if (splat && c->develop_splat.n != px * 3) c->develop_splat.alloc(px * 3);
+    if (c->develop_out.n < px * bpp) c->develop_out.alloc(px * 12);   // the largest format: allocated once
+    hipStream_t s = c->stream;
+    // the window's rows only, in both directions: they are one contiguous range of each buffer
+    const size_t r0 = (size_t)y0 * w, nr = (size_t)(y1 - y0 + 1) * w;
+    HIPCHK(hipMemcpyAsync(c->film_dev.p + r0 * 4, film + r0 * 4, nr * 16, hipMemcpyHostToDevice, s));
+    if (splat) HIPCHK(hipMemcpyAsync(c->develop_splat.p + r0 * 3, splat + r0 * 3, nr * 12, hipMemcpyHostToDevice, s));
+    uint8_t* o = c->develop_out.p + r0 * bpp;
+    uint8_t* oh = static_cast<uint8_t*>(out) + r0 * bpp;
+    // a window narrower than the image leaves pixels of its rows untouched: they go up first
+    if (x0 != 0 || x1 != c->S.width - 1) HIPCHK(hipMemcpyAsync(o, oh, nr * bpp, hipMemcpyHostToDevice, s));
+    develop_launch(c, dp, c->film_dev.p, splat ? c->develop_splat.p : nullptr, c->develop_out.p);
+    HIPCHK(hipMemcpyAsync(oh, o, nr * bpp, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     return BLING_OK;
   });
 }

@@ -16,6 +16,7 @@
 
 #include "../../../include/bling.h"
 #include "../common/scene_features.h"
+#include "../common/gamma_table.h"
 #include "bvh_build.h"
 #include "wavefront.h"
 #include "sppm.h"
@@ -143,6 +144,16 @@ struct MltState {
 
 }  // namespace bcore
 
+struct bling_ctx;
+namespace bcore {
+// film_develop.hip: bytes per pixel of a BLING_DEVELOP_* format; the window clipped to the uploaded
+// scene's image (false: empty); the threshold table's upload; one develop launch on the context's stream
+size_t develop_pixel_bytes(int format);
+bool develop_clip(const bling_ctx* c, const int32_t* window, int* x0, int* x1, int* y0, int* y1);
+void develop_table(bling_ctx* c);
+void develop_launch(bling_ctx* c, const bling_develop_params* dp, const float* film, const float* splat, void* out);
+}  // namespace bcore
+
 // the context lives in the global namespace (include/bling.h declares `struct bling_ctx`)
 using namespace bd;
 using namespace bcore;
@@ -230,6 +241,11 @@ struct bling_ctx {
   uint64_t stream_bytes[2 * BLING_N_STREAMS] = {};   // Counters::sb of the last pass (BLING_STREAM_STATS)
   DBuf<DevScene> dscene;      // the DevScene record in device memory (kernels take a pointer)
   DBuf<float> film_dev;
+  // bling_film_develop (film_develop.hip): rgbPixels' threshold table, uploaded with the context, and
+  // the host variant's staging buffers for the splat image and the developed image (the film stages
+  // through film_dev)
+  DBuf<float> gamma_tab, develop_splat;
+  DBuf<uint8_t> develop_out;
   // trace scratch
   DBuf<float> tr_rays, tr_t, tr_bary;
   DBuf<uint32_t> tr_prim;

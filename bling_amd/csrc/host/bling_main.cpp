@@ -3,6 +3,9 @@
 // pass-NNNNN.png and .hdr at PassDone) over the host loader and the MI355X core.
 //
 //   bling <scene.bling> [--overrides "image=W,H;..."] [--passes N] [--out prefix] [--device D]
+//         [--develop host|device]
+// --develop device makes each written pass's 8-bit and RGBE pixels on the device (bling_film_develop)
+// and hands them to the encoders; the default, host, develops with the host library.  Same files.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -13,20 +16,62 @@
 #include "bling.h"
 #include "bling_host.h"
 
+namespace {
+// One written pass: <name>.png and <name>.hdr.  On the device: RGB8 and RGBE through bling_film_develop
+// and the two pixel encoders; on the host: today's path.  splat may be NULL (then sw is unused).
+int write_pass(bling_ctx* ctx, bool on_device, const std::string& name, const float* film, const float* splat, float sw,
+               int w, int h, std::vector<float>& rgb) {
+  const std::string png = name + ".png", hdr = name + ".hdr";
+  if (on_device) {
+    std::vector<unsigned char> px8((size_t)w * h * 3), pxe((size_t)w * h * 4);
+    bling_develop_params dp{BLING_DEVELOP_RGB8, splat ? sw : 0.f, {0, w - 1, 0, h - 1}};
+    if (bling_film_develop(ctx, &dp, film, splat, px8.data()) != 0) { std::fprintf(stderr, "%s\n", bling_last_error()); return 1; }
+    dp.format = BLING_DEVELOP_RGBE;
+    if (bling_film_develop(ctx, &dp, film, splat, pxe.data()) != 0) { std::fprintf(stderr, "%s\n", bling_last_error()); return 1; }
+    if (bling_host_write_png_rgb8(png.c_str(), px8.data(), w, h) != 0 || bling_host_write_hdr_rgbe(hdr.c_str(), pxe.data(), w, h) != 0) {
+      std::fprintf(stderr, "%s\n", bling_host_last_error());
+      return 1;
+    }
+    return 0;
+  }
+  int rc;
+  if (splat) {
+    bling_host_film_splat_to_rgb(film, splat, sw, w, h, rgb.data());
+    rc = bling_host_write_png_splat(png.c_str(), film, splat, sw, w, h);
+  } else {
+    bling_host_film_to_rgb(film, w, h, rgb.data());
+    rc = bling_host_write_png(png.c_str(), film, w, h);
+  }
+  if (rc != 0 || bling_host_write_hdr(hdr.c_str(), rgb.data(), w, h) != 0) {
+    std::fprintf(stderr, "%s\n", bling_host_last_error());
+    return 1;
+  }
+  return 0;
+}
+}  // namespace
+
 int main(int argc, char** argv) {
   if (argc < 2) {
-    std::fprintf(stderr, "usage: %s scene.bling [--overrides S] [--passes N] [--out prefix] [--device D]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s scene.bling [--overrides S] [--passes N] [--out prefix] [--device D] [--develop host|device]\n", argv[0]);
     return 2;
   }
   const char* scene = argv[1];
   const char* ov = nullptr;
   const char* out = "pass";
   int passes = 1, device = 0;
+  bool dev_develop = false;
   for (int i = 2; i + 1 < argc; i += 2) {
     if (!std::strcmp(argv[i], "--overrides")) ov = argv[i + 1];
     else if (!std::strcmp(argv[i], "--passes")) passes = std::atoi(argv[i + 1]);
     else if (!std::strcmp(argv[i], "--out")) out = argv[i + 1];
     else if (!std::strcmp(argv[i], "--device")) device = std::atoi(argv[i + 1]);
+    else if (!std::strcmp(argv[i], "--develop")) {
+      if (std::strcmp(argv[i + 1], "host") && std::strcmp(argv[i + 1], "device")) {
+        std::fprintf(stderr, "--develop takes host or device, not %s\n", argv[i + 1]);
+        return 2;
+      }
+      dev_develop = !std::strcmp(argv[i + 1], "device");
+    }
   }
   bling_host_scene* hs = nullptr;
   if (bling_host_load(scene, ov, &hs) != 0) { std::fprintf(stderr, "%s\n", bling_host_last_error()); return 1; }
@@ -52,12 +97,7 @@ int main(int argc, char** argv) {
       char name[512];
       std::snprintf(name, sizeof name, "%s-%05d", out, p);
       std::printf("Writing %s...\n", name);
-      bling_host_film_splat_to_rgb(film.data(), splat.data(), sw, w, h, rgb.data());
-      if (bling_host_write_png_splat((std::string(name) + ".png").c_str(), film.data(), splat.data(), sw, w, h) != 0 ||
-          bling_host_write_hdr((std::string(name) + ".hdr").c_str(), rgb.data(), w, h) != 0) {
-        std::fprintf(stderr, "%s\n", bling_host_last_error());
-        return 1;
-      }
+      if (write_pass(ctx, dev_develop, name, film.data(), splat.data(), sw, w, h, rgb) != 0) return 1;
     }
     bling_destroy(ctx);
     bling_host_free(hs);
@@ -80,12 +120,7 @@ int main(int argc, char** argv) {
       char name[512];
       std::snprintf(name, sizeof name, "%s-%05d", out, p);
       std::printf("Writing %s...\n", name);
-      bling_host_film_splat_to_rgb(film.data(), splat.data(), sw, w, h, rgb.data());
-      if (bling_host_write_png_splat((std::string(name) + ".png").c_str(), film.data(), splat.data(), sw, w, h) != 0 ||
-          bling_host_write_hdr((std::string(name) + ".hdr").c_str(), rgb.data(), w, h) != 0) {
-        std::fprintf(stderr, "%s\n", bling_host_last_error());
-        return 1;
-      }
+      if (write_pass(ctx, dev_develop, name, film.data(), splat.data(), sw, w, h, rgb) != 0) return 1;
     }
     bling_destroy(ctx);
     bling_host_free(hs);
@@ -102,12 +137,7 @@ int main(int argc, char** argv) {
     char name[512];
     std::snprintf(name, sizeof name, "%s-%05d", out, p);
     std::printf("Writing %s...\n", name);
-    bling_host_film_to_rgb(film.data(), w, h, rgb.data());
-    if (bling_host_write_png((std::string(name) + ".png").c_str(), film.data(), w, h) != 0 ||
-        bling_host_write_hdr((std::string(name) + ".hdr").c_str(), rgb.data(), w, h) != 0) {
-      std::fprintf(stderr, "%s\n", bling_host_last_error());
-      return 1;
-    }
+    if (write_pass(ctx, dev_develop, name, film.data(), nullptr, 0.f, w, h, rgb) != 0) return 1;
   }
   bling_destroy(ctx);
   bling_host_free(hs);

@@ -25,6 +25,7 @@
 #include "../common/spectral_data.h"
 #include "../common/sky_model.h"
 #include "../common/cr_math.h"
+#include "../common/gamma_table.h"
 #include "hmath.h"
 #include "image_io.h"
 
@@ -1521,31 +1522,21 @@ void bling_host_film_splat_to_rgb(const float* film, const float* splat, float s
   }
 }
 
+// gamma 2.2 (Float `**` = powf of 1/2.2), clamp with GHC's max / min, * 255, round half to even:
+// bgamma::host_byte (common/gamma_table.h), the expression the device's threshold table is made from
 void bling_host_rgb_pixels_splat(const float* film, const float* splat, float sw, int w, int h, unsigned char* out) {
-  const float xg = 1.f / 2.2f;                                    // gamma x = let x' = 1 / x
-  auto hmax = [](float a, float b) { return a <= b ? b : a; };    // GHC Ord Float max / min
-  auto hmin = [](float a, float b) { return a <= b ? a : b; };
   std::vector<float> rgb((size_t)3 * w * h);
   bling_host_film_splat_to_rgb(film, splat, sw, w, h, rgb.data());
-  for (size_t i = 0; i < rgb.size(); ++i) {
-    float g = std::pow(rgb[i], xg);                               // r ** x' (powf)
-    float c = hmin(1.f, hmax(0.f, g)) * 255.f;
-    out[i] = (unsigned char)(int)std::nearbyint(c);               // round: half to even
-  }
+  for (size_t i = 0; i < rgb.size(); ++i) out[i] = bgamma::host_byte(rgb[i]);
 }
 
 void bling_host_rgb_pixels(const float* film, int w, int h, unsigned char* out) {
-  const float xg = 1.f / 2.2f;                                    // gamma x = let x' = 1 / x
-  auto hmax = [](float a, float b) { return a <= b ? b : a; };    // GHC Ord Float max / min
-  auto hmin = [](float a, float b) { return a <= b ? a : b; };
   std::vector<float> rgb((size_t)3 * w * h);
   bling_host_film_to_rgb(film, w, h, rgb.data());
-  for (size_t i = 0; i < rgb.size(); ++i) {
-    float g = std::pow(rgb[i], xg);                               // r ** x' (powf)
-    float c = hmin(1.f, hmax(0.f, g)) * 255.f;
-    out[i] = (unsigned char)(int)std::nearbyint(c);               // round: half to even
-  }
+  for (size_t i = 0; i < rgb.size(); ++i) out[i] = bgamma::host_byte(rgb[i]);
 }
+
+void bling_host_gamma_thresholds(float* out255) { bgamma::thresholds(out255); }
 
 namespace {
 uint32_t crc32_png(const unsigned char* p, size_t n, uint32_t c = 0xFFFFFFFFu) {
@@ -1584,12 +1575,18 @@ int bling_host_write_png_splat(const char* path, const float* film, const float*
   std::vector<unsigned char> px((size_t)3 * w * h);
   if (splat) bling_host_rgb_pixels_splat(film, splat, sw, w, h, px.data());
   else bling_host_rgb_pixels(film, w, h, px.data());
+  return bling_host_write_png_rgb8(path, px.data(), w, h);
+}
+
+int bling_host_write_png_rgb8(const char* path, const unsigned char* px, int w, int h) {
+  if (w <= 0 || h <= 0) { g_err = "empty image"; return -1; }
+  if (!px) { g_err = "null pixels"; return -1; }
   // raw scanlines, filter type 0
   std::vector<unsigned char> raw;
   raw.reserve((size_t)h * (3 * w + 1));
   for (int y = 0; y < h; ++y) {
     raw.push_back(0);
-    raw.insert(raw.end(), px.begin() + (size_t)3 * w * y, px.begin() + (size_t)3 * w * (y + 1));
+    raw.insert(raw.end(), px + (size_t)3 * w * y, px + (size_t)3 * w * (y + 1));
   }
   // zlib stream of stored deflate blocks (<= 65535 bytes each) + Adler-32
   std::vector<unsigned char> z = {0x78, 0x01};
@@ -1621,21 +1618,27 @@ int bling_host_write_png_splat(const char* path, const float* film, const float*
 }
 
 int bling_host_write_hdr(const char* path, const float* rgb, int w, int h) {
-  FILE* f = std::fopen(path, "wb");
-  if (!f) { g_err = std::string("cannot write ") + path; return -1; }
-  std::fprintf(f, "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y %d +X %d\n", h, w);
+  std::vector<unsigned char> px((size_t)4 * std::max(0, w) * std::max(0, h));
   for (int i = 0; i < w * h; ++i) {
     float r = std::max(0.f, rgb[3 * i]), g = std::max(0.f, rgb[3 * i + 1]), b = std::max(0.f, rgb[3 * i + 2]);
     float m = std::max(r, std::max(g, b));
-    unsigned char e[4] = {0, 0, 0, 0};
+    unsigned char* e = &px[(size_t)4 * i];                        // four zero bytes below 1e-32
     if (m >= 1e-32f) {
       int ex;
       float sc = std::frexp(m, &ex) * 256.f / m;
       e[0] = (unsigned char)(r * sc); e[1] = (unsigned char)(g * sc); e[2] = (unsigned char)(b * sc);
       e[3] = (unsigned char)(ex + 128);
     }
-    std::fwrite(e, 1, 4, f);
   }
+  return bling_host_write_hdr_rgbe(path, px.data(), w, h);
+}
+
+int bling_host_write_hdr_rgbe(const char* path, const unsigned char* rgbe, int w, int h) {
+  if (!rgbe && w > 0 && h > 0) { g_err = "null pixels"; return -1; }
+  FILE* f = std::fopen(path, "wb");
+  if (!f) { g_err = std::string("cannot write ") + path; return -1; }
+  std::fprintf(f, "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y %d +X %d\n", h, w);
+  if (w > 0 && h > 0) std::fwrite(rgbe, 1, (size_t)4 * w * h, f);
   std::fclose(f);
   return 0;
 }

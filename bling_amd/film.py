@@ -6,6 +6,9 @@ Reference (src/lib/Graphics/Bling):
   * ``writePng`` / ``writeRgbe`` (IO/Bitmap.hs:37-41)                     -> :func:`write_png`, :func:`write_hdr`
   * ``progressWriter`` (IO/Progress.hs:23-36): ``<base>-NNNNN.png`` and ``.hdr`` at every PassDone
     -> :func:`progress_writer`
+  * pixels that are already developed, e.g. on the device by ``Context.develop``
+    -> :func:`write_png_rgb8`, :func:`write_hdr_rgbe`; the table its 8-bit bytes are looked up in
+    -> :func:`gamma_thresholds`
 The film is the (W, X, Y, Z) array a pass accumulates (``bling_render_pass``), shape (h * w * 4,).
 """
 from __future__ import annotations
@@ -49,6 +52,36 @@ def write_png(path: str, film, w: int, h: int) -> None:
 def write_hdr(path: str, film, w: int, h: int) -> None:
     rgb = np.ascontiguousarray(to_rgb(film, w, h).reshape(-1))
     if _ffi.host().bling_host_write_hdr(path.encode(), _ffi.f32ptr(rgb), w, h) != 0:
+        raise OSError(_ffi.host().bling_host_last_error().decode())
+
+
+def gamma_thresholds() -> np.ndarray:
+    """bling_host_gamma_thresholds: rgbPixels' float -> byte step as 255 ascending float32 thresholds;
+    the byte of a linear channel v is the count of thresholds <= v (the table Context.develop's
+    "rgb8" looks up on the device)."""
+    t = np.zeros(255, np.float32)
+    _ffi.host().bling_host_gamma_thresholds(_ffi.f32ptr(t))
+    return t
+
+
+def _pixels(px, w, h, per):
+    p = np.ascontiguousarray(px, np.uint8).reshape(-1)
+    if p.size != w * h * per:
+        raise ValueError(f"image has {p.size} bytes, expected {w} x {h} x {per}")
+    return p
+
+
+def write_png_rgb8(path: str, rgb8, w: int, h: int) -> None:
+    """The PNG of write_png for pixels that are already developed (Context.develop's "rgb8")."""
+    p = _pixels(rgb8, w, h, 3)
+    if _ffi.host().bling_host_write_png_rgb8(path.encode(), p.ctypes.data_as(C.POINTER(C.c_uint8)), w, h) != 0:
+        raise OSError(_ffi.host().bling_host_last_error().decode())
+
+
+def write_hdr_rgbe(path: str, rgbe, w: int, h: int) -> None:
+    """The Radiance file of write_hdr for RGBE bytes that are already made (Context.develop's "rgbe")."""
+    p = _pixels(rgbe, w, h, 4)
+    if _ffi.host().bling_host_write_hdr_rgbe(path.encode(), p.ctypes.data_as(C.POINTER(C.c_uint8)), w, h) != 0:
         raise OSError(_ffi.host().bling_host_last_error().decode())
 
 

@@ -242,6 +242,72 @@ class Context:
         arr = (C.c_void_p * world)(*[C.c_void_p(p) for p, _ in bufs])
         _check(_ffi.hip().bling_film_add_shards(self._h, C.byref(pp), arr, C.c_void_p(film_ptr)))
 
+    # fmt -> (BLING_DEVELOP_*, element type, elements per pixel)
+    _DEVELOP = {"rgb_f32": (_ffi.DEVELOP_RGB_F32, "float32", 3), "rgb8": (_ffi.DEVELOP_RGB8, "uint8", 3),
+                "rgbe": (_ffi.DEVELOP_RGBE, "uint8", 4)}
+
+    @staticmethod
+    def _develop_tensor(buf, what, dtype, numel):
+        """Device pointer of a tensor-like buffer (data_ptr() and numel(), as _tiles_buf) after checking
+        its element type, its size and that it lives on a device."""
+        if not (hasattr(buf, "data_ptr") and hasattr(buf, "numel")):
+            raise ValueError(f"develop: {what} must be a device tensor")
+        dt = getattr(buf, "dtype", None)
+        if dt is not None and str(dt) not in ("torch." + dtype, dtype):
+            raise ValueError(f"develop: {what} must be {dtype}, got {dt}")
+        if hasattr(buf, "is_cuda") and not buf.is_cuda:
+            raise ValueError(f"develop: {what} must be a device tensor")
+        if hasattr(buf, "is_contiguous") and not buf.is_contiguous():
+            raise ValueError(f"develop: {what} must be contiguous")
+        if int(buf.numel()) != numel:
+            raise ValueError(f"develop: {what} has {int(buf.numel())} elements, expected {numel}")
+        return int(buf.data_ptr())
+
+    def develop(self, film, splat=None, splat_weight=0.0, fmt="rgb8", window=None, out=None):
+        """bling_film_develop[_device]: the film (W, X, Y, Z; w * h * 4) and an optional splat image
+        (X, Y, Z; w * h * 3) with its weight as a display image, made on the device: fmt "rgb_f32"
+        (linear RGB, float32 h x w x 3: getPixel + xyzToRgb), "rgb8" (rgbPixels' bytes, uint8 h x w x 3)
+        or "rgbe" (writeRgbe's bytes, uint8 h x w x 4), each equal to the host library's.  window =
+        (x0, x1, y0, y1), inclusive and clipped to the image, develops those pixels only and leaves the
+        rest of out as it was; None is the whole image.
+        A numpy film takes the host variant: film and splat are staged to the device, and only the
+        image comes back; returns a numpy array (out, if given: a C-contiguous array of the image's
+        element type and size).  A tensor-like film (data_ptr() and numel(), e.g. a torch tensor on
+        this context's first device) takes the device variant: splat, if given, and out (required)
+        are device tensors too, out is written in place and returned.  The call runs on the
+        context's own stream: work of another stream on these tensors must have finished."""
+        if fmt not in self._DEVELOP:
+            raise ValueError(f"develop: unknown format {fmt!r} (rgb_f32, rgb8, rgbe)")
+        code, dtype, per = self._DEVELOP[fmt]
+        if self.job is None:
+            raise BlingError(-4, "no scene uploaded")   # BLING_ENOSCENE: the image size is the scene's
+        w, h = self.job.width, self.job.height
+        win =(0, w - 1, 0, h - 1) if window is None else tuple(int(v) for v in window)
+        if len(win) != 4:
+            raise ValueError("develop: window is (x0, x1, y0, y1)")
+        dp = _ffi.DevelopParams(code, float(np.float32(splat_weight)), (C.c_int32 * 4)(*win))
+        lib = _ffi.hip()
+        if isinstance(film, np.ndarray):
+            f = np.ascontiguousarray(film, np.float32).reshape(-1)
+            s = None if splat is None else np.ascontiguousarray(splat, np.float32).reshape(-1)
+            if self.job is not None and (f.size != w * h * 4 or (s is not None and s.size != w * h * 3)):
+                raise ValueError(f"develop: film / splat sizes do not match the {w} x {h} image")
+            if out is None:
+                out = np.zeros((h, w, per), dtype)
+            elif not (isinstance(out, np.ndarray) and out.dtype == np.dtype(dtype) and out.size == w * h * per
+                      and out.flags.c_contiguous):
+                raise ValueError(f"develop: out must be a C-contiguous {dtype} array of {w * h * per} elements")
+            _check(lib.bling_film_develop(self._h, C.byref(dp), _ffi.f32ptr(f), None if s is None else _ffi.f32ptr(s),
+                                          C.c_void_p(out.ctypes.data)))
+            return out
+        fp = self._develop_tensor(film, "film", "float32", w * h * 4)
+        sp = None if splat is None else self._develop_tensor(splat, "splat", "float32", w * h * 3)
+        if out is None:
+            raise ValueError("develop: a device film needs out, a device tensor to write into")
+        op = self._develop_tensor(out, "out", dtype, w * h * per)
+        _check(lib.bling_film_develop_device(self._h, C.byref(dp), C.c_void_p(fp), C.c_void_p(sp), C.c_void_p(op)))
+        return out
+
     def trace(self, rays_soa: np.ndarray, any_hit: bool = False):
         """Scene.scIntersect / Scene.occluded for a batch of rays (8 x n SoA)."""
         rays_soa = np.ascontiguousarray(rays_soa, np.float32)

@@ -207,6 +207,49 @@ int bling_film_add_tiles(bling_ctx* ctx, const bling_pass_params* p, const void*
 int bling_film_add_shards(bling_ctx* ctx, const bling_pass_params* p, const void* const* tiles_devices,
                           void* film_device);
 
+/* Replaces: getPixel + xyzToRgb (Image.hs:302-315), rgbPixels (Image.hs:317-331) and the pixel loop of
+ * writeRgbe (IO/Bitmap.hs:36-41) -- the develop step of progressWriter's PassDone and of the GUI's
+ * SamplesAdded -- for a film that lives on the device.  film: width*height*4 floats (W, X, Y, Z);
+ * splat: width*height*3 floats (XYZ) or NULL (= all zero); the pixel's XYZ is splat_weight * splat
+ * (+ film XYZ / W where W != 0).  Width and height are the uploaded scene's.  out is a whole-image
+ * buffer in one of three formats, row-major from the top:
+ *   BLING_DEVELOP_RGB_F32  width*height*3 floats, bit for bit bling_host_film_splat_to_rgb (a NaN is
+ *                          a NaN, of whatever payload);
+ *   BLING_DEVELOP_RGB8     width*height*3 bytes, byte for byte bling_host_rgb_pixels_splat: gamma 2.2,
+ *                          clamp, round half to even, looked up in the host library's table of 255
+ *                          thresholds (bling_host_gamma_thresholds) rather than computed with a device
+ *                          pow; NaN, finite negatives and +-0 give 0, +Inf gives 255 and so does
+ *                          -Inf (powf (-Inf) (1 / 2.2) is +Inf), which the lookup takes as +Inf;
+ *   BLING_DEVELOP_RGBE     width*height*4 bytes, the bytes bling_host_write_hdr puts after its header
+ *                          for that RGB image (a mantissa that rounds to 256 and the exponent byte of
+ *                          m >= 2^127 wrap to 0, as the host's do).  A pixel with a +Inf channel is
+ *                          outside that contract (the host's frexp exponent is unspecified there):
+ *                          the device writes 0, 0, 0, 1.
+ * window = x0, x1, y0, y1, inclusive, clipped to the image (as rgbPixels filters coverWindow): only its
+ * pixels are written and the rest of out stays as it was, so one buffer serves as a preview updated
+ * per SamplesAdded window; a window wholly outside the image (or x1 < x0, y1 < y0) writes nothing.
+ * Errors: BLING_ENOSCENE without a scene; BLING_EINVAL for a format other than the three, a NULL
+ * params / film / out, or an out that overlaps film or splat.  On a multi-device context the call runs
+ * on device_ids[0], where every film merge lands.  Both calls run on the context's stream and return
+ * after completion.
+ * bling_film_develop_device: film, splat and out are device buffers on device_ids[0], e.g. the film
+ * of bling_render_pass_device; nothing crosses to the host.
+ * bling_film_develop: film, splat and out are host buffers; film and splat are staged through device
+ * buffers the context owns (allocated once, reused) and only the developed rows come back: 3 or 4
+ * bytes per pixel for the byte formats instead of the film's 16. */
+#define BLING_DEVELOP_RGB_F32 0
+#define BLING_DEVELOP_RGB8    1
+#define BLING_DEVELOP_RGBE    2
+typedef struct bling_develop_params {
+    int32_t format;            /* BLING_DEVELOP_*                                               */
+    float   splat_weight;
+    int32_t window[4];         /* x0, x1, y0, y1, inclusive                                     */
+} bling_develop_params;
+int bling_film_develop_device(bling_ctx* ctx, const bling_develop_params* p, const void* film_dev,
+                              const void* splat_dev, void* out_dev);
+int bling_film_develop(bling_ctx* ctx, const bling_develop_params* p, const float* film_host,
+                       const float* splat_host, void* out_host);
+
 /* Replaces: Scene.scIntersect / Scene.occluded for a batch (Scene.hs:45-51 -> KdTree.hs:236-246).
  * rays_soa: 8 planes of n floats (ox, oy, oz, dx, dy, dz, tmin, tmax).
  * closest (any_hit=0): t_out[n], prim_out[n] (index into desc->prim_kind order, BLING_MISS on

@@ -70,6 +70,21 @@ void bling_host_rgb_pixels_splat(const float* film, const float* splat, float sw
                                  unsigned char* out_rgb8);
 int bling_host_write_png_splat(const char* path, const float* film, const float* splat, float sw, int w, int h);
 
+/* The float -> 8-bit step of rgbPixels as a table: out255[k], k = 0 .. 254, is the smallest binary32 v
+ * whose byte nearbyint(min(1, max(0, powf(v, 1/2.2f))) * 255) is at least k + 1, found by bisecting
+ * over float bit patterns with that very expression.  The byte of any v is then the count of
+ * out255[k] <= v (NaN, finite negatives and +-0 count none; +Inf counts all), except that -Inf, whose
+ * powf is +Inf, has the byte 255 and is looked up as +Inf.  bling_film_develop (bling.h)
+ * looks its RGB8 bytes up in this table, built by the same routine, instead of calling a device pow. */
+void bling_host_gamma_thresholds(float* out255);
+
+/* The encoders of the two writers above for pixels that are already developed, e.g. by
+ * bling_film_develop: rgb8 is w*h*3 bytes (BLING_DEVELOP_RGB8), rgbe w*h*4 bytes (BLING_DEVELOP_RGBE),
+ * row-major from the top.  bling_host_write_png[_splat] and bling_host_write_hdr go through them, so
+ * the same pixels give the same file. */
+int bling_host_write_png_rgb8(const char* path, const unsigned char* rgb8, int w, int h);
+int bling_host_write_hdr_rgbe(const char* path, const unsigned char* rgbe, int w, int h);
+
 #ifdef __cplusplus
 }
 #endif
