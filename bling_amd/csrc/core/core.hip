@@ -8,6 +8,8 @@
 // Path state is SoA (one 64-B record per spectrum) indexed through compacted queues.  Traversal
 // uses the LDS stack of dev_trace.h.
 #include "core_internal.h"
+#include "pass_plan.h"
+#include "pass_stats.h"
 
 #include <chrono>
 #include <cmath>
@@ -611,215 +613,167 @@ void launch_film(bling_ctx* c, const WaveState& P, const TileDesc* td, unsigned 
     k_film<<<n_tiles, 256, 0, s>>>(c->dscene.p, P, td, film_dev, timg, sw, sh);
 }
 
-int render(bling_ctx* c, const bling_pass_params* p, float* film_dev, bling_stats* st) {
-  const DevScene& S = c->S;
-  uint32_t spp = (uint32_t)S.spp;
-  const std::vector<TileDesc> tiles = pass_tiles(S, p->shard_rank, p->shard_world, p->tile_stride);
-  float* timg = (p->flags & BLING_PASS_TILE_IMAGES) ? static_cast<float*>(p->tiles_device) : nullptr;
-  if ((p->flags & BLING_PASS_TILE_IMAGES) && !timg) throw std::invalid_argument("BLING_PASS_TILE_IMAGES without tiles_device");
+struct PassPlan {                 // what render() settles before its first launch
+  std::vector<TileDesc> tiles;
+  std::vector<uint32_t> counts;   // the tiles' samples, for pass_plan.h
+  uint64_t total = 0;             // the pass's paths
+  uint32_t chunk = 0;             // paths per wave
+  bool pipe = false;              // one wave, at least two tiles: two half-waves cut at a tile boundary, in flight together
+  float* timg = nullptr;          // BLING_PASS_TILE_IMAGES: the tile images, slot_floats per tile
+  size_t slot_floats = 0;
+  float* timg_at(size_t tile) const { return timg ? timg + tile * slot_floats : nullptr; }
+};
+
+// Checks the pass's parameters, sizes its waves (pass_plan.h wave_chunk) and allocates their path state.
+PassPlan plan_pass(bling_ctx* c, const bling_pass_params* p) {
+  PassPlan pl;
+  pl.tiles = pass_tiles(c->S, p->shard_rank, p->shard_world, p->tile_stride);
+  pl.timg = (p->flags & BLING_PASS_TILE_IMAGES) ? static_cast<float*>(p->tiles_device) : nullptr;
+  if ((p->flags & BLING_PASS_TILE_IMAGES) && !pl.timg) throw std::invalid_argument("BLING_PASS_TILE_IMAGES without tiles_device");
   int slot_w, slot_h;
-  tile_slot(S, &slot_w, &slot_h);
-  const size_t slot_floats = (size_t)slot_w * slot_h * 4;
-  if (timg && p->tiles_capacity < tiles.size() * slot_floats)
+  tile_slot(c->S, &slot_w, &slot_h);
+  pl.slot_floats = (size_t)slot_w * slot_h * 4;
+  if (pl.timg && p->tiles_capacity < pl.tiles.size() * pl.slot_floats)
     throw std::invalid_argument("tiles_capacity " + std::to_string(p->tiles_capacity) + " floats < the " +
-                                std::to_string(tiles.size() * slot_floats) + " this shard's tile images need");
-  uint64_t total = 0;
-  for (auto& t : tiles) total += t.count;
-  // Default wave: the whole pass when it fits in half of the free HBM (C2: 67.7 M paths, ~33 GB
-  // of path state on a 288 GB MI355X) -- one wave means 8 launches per bounce in total instead of
-  // per chunk, and full-device waves at the deep bounces.
-  uint64_t want = p->chunk_paths > 0 ? (uint64_t)p->chunk_paths : total;
-  if (p->chunk_paths <= 0) {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0) {
-      // half of (free + what this context already holds): the same answer on every pass, so a
-      // pass never re-allocates the path state the previous one sized (C3: 140 GB per hipMalloc)
-      const uint64_t pb = c->path_bytes();
-      const uint64_t held = (uint64_t)c->cap * pb;
-      const uint64_t fit = std::max<uint64_t>(((uint64_t)free_b + held) / 2 / pb, 1u << 20);
-      if (want > fit) {
-        // equal waves instead of full waves plus a small remainder; one tile of slack because
-        // waves are cut at tile boundaries
-        uint32_t max_tile = 0;
-        for (auto& t : tiles) max_tile = std::max(max_tile, t.count);
-        const uint64_t waves = (total + fit - 1) / fit;
-        want = std::min<uint64_t>(fit, (total + waves - 1) / waves + max_tile);
-      }
-    } else {
-      want = std::min<uint64_t>(want, 1u << 22);
-    }
-  }
-  want = std::min<uint64_t>(want, (uint64_t)1 << 31);
-  uint32_t chunk = (uint32_t)std::max<uint64_t>(want, 256u * spp);
-  // one wave, at least two tiles: two half-waves cut at a tile boundary, in flight together
-  const bool pipe = total > 0 && total <= chunk && total + 256 < ((uint64_t)1 << 31) && tiles.size() >= 2 && pipeline_wanted(c, p);
+                                std::to_string(pl.tiles.size() * pl.slot_floats) + " this shard's tile images need");
+  uint32_t max_tile = 0;
+  for (auto& t : pl.tiles) { pl.counts.push_back(t.count); pl.total += t.count; max_tile = std::max(max_tile, t.count); }
+  size_t free_b = 0, total_b = 0;
+  const bool mem = p->chunk_paths <= 0 && hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0;
+  const uint64_t pb = c->path_bytes();
+  pl.chunk = pass_plan::wave_chunk(pl.total, max_tile, (uint32_t)c->S.spp, p->chunk_paths, mem, free_b, (uint64_t)c->cap * pb, pb);
+  pl.pipe = pl.total > 0 && pl.total <= pl.chunk && pl.total + 256 < ((uint64_t)1 << 31) && pl.tiles.size() >= 2 && pipeline_wanted(c, p);
   // (the first half's slots are rounded up to 256, so the pair needs up to 255 more than one wave)
-  c->ensure_paths((uint32_t)(std::min<uint64_t>(chunk, std::max<uint64_t>(total, 1)) + (pipe ? 256u : 0u)));
-  chunk = std::min<uint32_t>(chunk, c->cap);
+  c->ensure_paths((uint32_t)(std::min<uint64_t>(pl.chunk, std::max<uint64_t>(pl.total, 1)) + (pl.pipe ? 256u : 0u)));
+  pl.chunk = std::min<uint32_t>(pl.chunk, c->cap);
+  return pl;
+}
+
+struct PassRun {                  // what a pass adds up wave by wave, and the events it reuses for each wave
+  EventPair bounce;               // around a wave's path-vertex launches
+  Event film_end;                 // after its film
+  WaveTiming tm;
+  bling_stats st{};               // the samples, launches and times so far
+  std::vector<TileDesc> batch;    // the host's copy of a wave's tile table, kept until the wave's sync
+};
+
+// After the stream has finished a wave of n0 samples (waves = -2: the two half-waves of n0 and n1, the
+// second one's results off1 slots in): what bling_debug_pass_results reads, and the wave's times.
+void wave_done(bling_ctx* c, PassRun& r, int waves, uint32_t n0, uint32_t n1, uint32_t off1) {
+  r.st.camera_samples += (uint64_t)n0 + n1;
+  c->last_pass_waves = waves; c->last_n[0] = n0; c->last_n[1] = n1; c->last_off[1] = off1;
+  r.st.ms_bounce += r.bounce.elapsed_ms();
+  r.st.ms_film += elapsed_ms(r.bounce.b, r.film_end);
+  r.tm.harvest(r.st.ms_closest, r.st.closest_launches, r.st.ms_shade, r.st.shade_launches);
+}
+
+// Tiles t0 .. t0 + offset.size() - 1 with these sample offsets into the device's tile table.
+void upload_tiles(bling_ctx* c, const PassPlan& pl, PassRun& r, size_t t0, const std::vector<uint32_t>& offset) {
+  r.batch.assign(pl.tiles.begin() + t0, pl.tiles.begin() + t0 + offset.size());
+  for (size_t k = 0; k < offset.size(); ++k) r.batch[k].offset = offset[k];
+  HIPCHK(hipMemcpyAsync(c->tiles_dev.p, r.batch.data(), offset.size() * sizeof(TileDesc), hipMemcpyHostToDevice, c->stream));
+}
+
+// The pass as two half-waves on two streams (pass_plan.h half_cut, core_wave.h run_wave_pair_t).
+void render_pair(bling_ctx* c, const bling_pass_params* p, const PassPlan& pl, const WaveState& P, float* film_dev, PassRun& r) {
+  const pass_plan::HalfCut hc = pass_plan::half_cut(pl.counts);
+  const uint32_t cap_a = (hc.nh[0] + 255u) & ~255u;
+  if ((uint64_t)cap_a + hc.nh[1] > c->cap) throw std::runtime_error("half-waves exceed the path capacity");
+  c->ensure_half_streams();
+  const hipStream_t s = c->stream, hs[2] = {c->half_stream[0], c->half_stream[1]};
+  HalfWave H[2] = {{c->state_half(0, cap_a), hc.nh[0], hs[0], c->tiles_dev.p, (unsigned)hc.cut, hc.maxc[0]},
+                   {c->state_half(1, cap_a), hc.nh[1], hs[1], c->tiles_dev.p + hc.cut, (unsigned)(pl.tiles.size() - hc.cut), hc.maxc[1]}};
+  for (auto& h : H) h.W.mis_cull = P.mis_cull;
+  upload_tiles(c, pl, r, 0, hc.offset);
+  r.bounce.a.record(s);
+  // the halves start after everything enqueued so far (the tile table, the counters' reset, the
+  // previous pass's film), and the film waits for each of them
+  HIPCHK(hipEventRecord(c->half_fork, s));
+  try {
+    for (int h = 0; h < 2; ++h) HIPCHK(hipStreamWaitEvent(hs[h], c->half_fork, 0));
+    r.st.bounce_launches += (uint64_t)run_wave_pair(c, H, p->seed, p->pass_index, (p->flags & BLING_PASS_TRAVERSAL_STATS) != 0, &r.tm);
+    for (int h = 0; h < 2; ++h) {
+      HIPCHK(hipEventRecord(c->half_done[h], hs[h]));
+      HIPCHK(hipStreamWaitEvent(s, c->half_done[h], 0));
+      if (h == 1) r.bounce.b.record(s);
+      launch_film(c, H[h].W, H[h].td, H[h].n_tiles, film_dev, pl.timg_at(h ? hc.cut : 0));
+    }
+    r.film_end.record(s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+  } catch (...) {
+    // an error between the fork and the join: nothing of the halves may still run on the context's
+    // buffers when the caller sees it (the next pass, or ensure_paths, would reuse or free them)
+    for (int h = 0; h < 2; ++h) (void)hipStreamSynchronize(hs[h]);
+    (void)hipStreamSynchronize(s);
+    throw;
+  }
+  // ms_film: the second half's film only (the first half's runs beside the second half's last
+  // launches); ms_bounce: from the halves' start to the end of the later one
+  wave_done(c, r, -2, hc.nh[0], hc.nh[1], cap_a);
+}
+
+// st with a pass's device counters filled in.  bling_sample_li reports path_vertices for the
+// bidirectional and the normal-map integrator only, and no traversal counts.
+bling_stats stats_from_counters(const Counters& hc, bling_stats st, bool vertices, bool traversal) {
+  st.rays_camera = hc.cam; st.rays_continuation = hc.cont; st.rays_mis = hc.mis; st.rays_shadow = hc.shadow;
+  st.dropped_samples = hc.dropped; st.path_vertices = vertices ? hc.vertices : 0;
+  if (traversal) {
+    st.node_visits = hc.node_visits; st.tri_tests = hc.tri_tests; st.shape_tests = hc.shape_tests; st.march_ticks = hc.march_ticks;
+    st.closest_node_visits = hc.c_node_visits; st.closest_tri_tests = hc.c_tri_tests;
+    st.closest_shape_tests = hc.c_shape_tests; st.closest_march_ticks = hc.c_march_ticks;
+  }
+  return st;
+}
+
+int render(bling_ctx* c, const bling_pass_params* p, float* film_dev, bling_stats* st) {
+  const PassPlan pl = plan_pass(c, p);
   WaveState P = c->state();
   if (p->flags & BLING_PASS_NO_MIS_CULL) P.mis_cull = 0u;
   c->last_pass_waves = 0;
   hipStream_t s = c->stream;
   HIPCHK(hipMemsetAsync(c->counters.p, 0, sizeof(Counters), s));
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-  hipEvent_t eb0, eb1, ef1;
-  HIPCHK(hipEventCreate(&eb0)); HIPCHK(hipEventCreate(&eb1)); HIPCHK(hipEventCreate(&ef1));
-  HIPCHK(hipEventRecord(e0, s));
-  uint64_t samples = 0, launches = 0;
-  const bool stats_on = (p->flags & BLING_PASS_TRAVERSAL_STATS) != 0;
-  WaveTiming tm;
-  tm.on = (p->flags & BLING_PASS_KERNEL_TIMING) != 0;
-  double ms_closest = 0.0, ms_shade = 0.0;
-  uint64_t n_closest = 0, n_shade = 0;
-  double ms_bounce = 0.0, ms_film = 0.0;
-  size_t t0 = 0;
-  std::vector<TileDesc> batch;
-  c->tiles_dev.alloc(std::max<size_t>(1, tiles.size()));
-  if (pipe) {
-    // the cut: the first tile boundary at or past half of the paths (total > 0: the first half is not empty)
-    size_t cut = 0;
-    uint32_t nh[2] = {0u, 0u};
-    while (cut + 1 < tiles.size() && 2 * (uint64_t)nh[0] < total) nh[0] += tiles[cut++].count;
-    uint32_t maxc[2] = {0u, 0u}, run[2] = {0u, 0u};
-    for (size_t k = 0; k < tiles.size(); ++k) {      // each half's sample ids start at 0
-      const int h = k < cut ? 0 : 1;
-      TileDesc t = tiles[k];
-      t.offset = run[h]; run[h] += t.count;
-      maxc[h] = std::max(maxc[h], t.count);
-      batch.push_back(t);
-    }
-    nh[1] = run[1];
-    const uint32_t cap_a = (nh[0] + 255u) & ~255u;
-    if ((uint64_t)cap_a + nh[1] > c->cap) throw std::runtime_error("half-waves exceed the path capacity");
-    c->ensure_half_streams();
-    const hipStream_t hs[2] = {c->half_stream[0], c->half_stream[1]};
-    HalfWave H[2] = {{c->state_half(0, cap_a), nh[0], hs[0], c->tiles_dev.p, (unsigned)cut, maxc[0]},
-                     {c->state_half(1, cap_a), nh[1], hs[1], c->tiles_dev.p + cut, (unsigned)(tiles.size() - cut), maxc[1]}};
-    for (auto& h : H) h.W.mis_cull = P.mis_cull;
-    HIPCHK(hipMemcpyAsync(c->tiles_dev.p, batch.data(), batch.size() * sizeof(TileDesc), hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(eb0, s));
-    // the halves start after everything enqueued so far (the tile table, the counters' reset, the
-    // previous pass's film), and the film waits for each of them
-    HIPCHK(hipEventRecord(c->half_fork, s));
-    try {
-      for (int h = 0; h < 2; ++h) HIPCHK(hipStreamWaitEvent(hs[h], c->half_fork, 0));
-      launches += (uint64_t)run_wave_pair(c, H, p->seed, p->pass_index, stats_on, &tm);
-      for (int h = 0; h < 2; ++h) {
-        HIPCHK(hipEventRecord(c->half_done[h], hs[h]));
-        HIPCHK(hipStreamWaitEvent(s, c->half_done[h], 0));
-        if (h == 1) HIPCHK(hipEventRecord(eb1, s));
-        launch_film(c, H[h].W, H[h].td, H[h].n_tiles, film_dev, timg ? timg + (h ? cut : 0) * slot_floats : nullptr);
-      }
-      HIPCHK(hipEventRecord(ef1, s));
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipStreamSynchronize(s));
-    } catch (...) {
-      // an error between the fork and the join: nothing of the halves may still run on the context's
-      // buffers when the caller sees it (the next pass, or ensure_paths, would reuse or free them)
-      for (int h = 0; h < 2; ++h) (void)hipStreamSynchronize(hs[h]);
-      (void)hipStreamSynchronize(s);
-      throw;
-    }
-    samples += (uint64_t)nh[0] + nh[1];
-    c->last_pass_waves = -2;            // bling_debug_pass_results: two half-waves in flight together
-    c->last_n[0] = nh[0]; c->last_n[1] = nh[1]; c->last_off[1] = cap_a;
-    t0 = tiles.size();
-    // ms_film: the second half's film only (the first half's runs beside the second half's last
-    // launches); ms_bounce: from the halves' start to the end of the later one
-    float a = 0.f, b = 0.f;
-    HIPCHK(hipEventElapsedTime(&a, eb0, eb1));
-    HIPCHK(hipEventElapsedTime(&b, eb1, ef1));
-    ms_bounce += a; ms_film += b;
-    for (auto* ev : {&tm.ev, &tm.ev_shade}) {
-      for (size_t k = 0; k + 1 < ev->size(); k += 2) {
-        float m = 0.f;
-        HIPCHK(hipEventElapsedTime(&m, (*ev)[k], (*ev)[k + 1]));
-        if (ev == &tm.ev) { ms_closest += m; ++n_closest; } else { ms_shade += m; ++n_shade; }
-        (void)hipEventDestroy((*ev)[k]); (void)hipEventDestroy((*ev)[k + 1]);
-      }
-      ev->clear();
-    }
-  }
-  int n_waves = 0;
-  while (t0 < tiles.size()) {
-    batch.clear();
-    uint32_t off = 0, maxc = 0;
-    size_t t1 = t0;
-    while (t1 < tiles.size() && off + tiles[t1].count <= chunk) {
-      TileDesc t = tiles[t1]; t.offset = off; off += t.count; maxc = std::max(maxc, t.count); batch.push_back(t); ++t1;
-    }
-    HIPCHK(hipMemcpyAsync(c->tiles_dev.p, batch.data(), batch.size() * sizeof(TileDesc), hipMemcpyHostToDevice, s));
-    if (S.integrator == BLING_INTEGRATOR_BIDIR) {
-      HIPCHK(hipEventRecord(eb0, s));
-      launches += (uint64_t)bidir_wave(c, P, c->tiles_dev.p, (unsigned)batch.size(), maxc, nullptr, off, p->seed,
-                                           p->pass_index, nullptr);
+  const EventPair pass;
+  pass.a.record(s);
+  PassRun r;
+  r.tm.on = (p->flags & BLING_PASS_KERNEL_TIMING) != 0;
+  c->tiles_dev.alloc(std::max<size_t>(1, pl.tiles.size()));
+  if (pl.pipe) render_pair(c, p, pl, P, film_dev, r);
+  for (size_t t0 = pl.pipe ? pl.tiles.size() : 0; t0 < pl.tiles.size();) {
+    const pass_plan::Wave w = pass_plan::next_wave(pl.counts, t0, pl.chunk);
+    const unsigned nt = (unsigned)(w.t1 - t0);
+    upload_tiles(c, pl, r, t0, w.offset);
+    if (c->S.integrator == BLING_INTEGRATOR_BIDIR) {
+      r.bounce.a.record(s);
+      r.st.bounce_launches += (uint64_t)bidir_wave(c, P, c->tiles_dev.p, nt, w.maxc, nullptr, w.off, p->seed, p->pass_index, nullptr);
     } else {
-      dim3 g((maxc + 255) / 256, (unsigned)batch.size());
-      k_reset_queues<<<1, 64, 0, s>>>(P.qcount, off);
-      k_raygen<<<g, 256, 0, s>>>(c->dscene.p, P, c->tiles_dev.p, p->seed, p->pass_index);
-      HIPCHK(hipEventRecord(eb0, s));
-      if (S.integrator == BLING_INTEGRATOR_NORMALS) launches += (uint64_t)normals_wave(c, P, off, &tm);
-      else launches += (uint64_t)run_wave(c, P, off, p->seed, p->pass_index, stats_on, &tm);
+      k_reset_queues<<<1, 64, 0, s>>>(P.qcount, w.off);
+      k_raygen<<<dim3((w.maxc + 255) / 256, nt), 256, 0, s>>>(c->dscene.p, P, c->tiles_dev.p, p->seed, p->pass_index);
+      r.bounce.a.record(s);
+      if (c->S.integrator == BLING_INTEGRATOR_NORMALS) r.st.bounce_launches += (uint64_t)normals_wave(c, P, w.off, &r.tm);
+      else r.st.bounce_launches += (uint64_t)run_wave(c, P, w.off, p->seed, p->pass_index, (p->flags & BLING_PASS_TRAVERSAL_STATS) != 0, &r.tm);
     }
-    HIPCHK(hipEventRecord(eb1, s));
-    launch_film(c, P, c->tiles_dev.p, (unsigned)batch.size(), film_dev, timg ? timg + t0 * slot_floats : nullptr);
-    HIPCHK(hipEventRecord(ef1, s));
+    r.bounce.b.record(s);
+    launch_film(c, P, c->tiles_dev.p, nt, film_dev, pl.timg_at(t0));
+    r.film_end.record(s);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));   // the tile table is reused by the next chunk
-    samples += off;
-    t0 = t1;
-    c->last_pass_waves = ++n_waves;
-    c->last_n[0] = off; c->last_n[1] = 0; c->last_off[1] = 0;
-    float a = 0.f, b = 0.f;
-    HIPCHK(hipEventElapsedTime(&a, eb0, eb1));
-    HIPCHK(hipEventElapsedTime(&b, eb1, ef1));
-    ms_bounce += a; ms_film += b;
-    for (size_t k = 0; k + 1 < tm.ev.size(); k += 2) {
-      float m = 0.f;
-      HIPCHK(hipEventElapsedTime(&m, tm.ev[k], tm.ev[k + 1]));
-      ms_closest += m; ++n_closest;
-      (void)hipEventDestroy(tm.ev[k]); (void)hipEventDestroy(tm.ev[k + 1]);
-    }
-    tm.ev.clear();
-    for (size_t k = 0; k + 1 < tm.ev_shade.size(); k += 2) {
-      float m = 0.f;
-      HIPCHK(hipEventElapsedTime(&m, tm.ev_shade[k], tm.ev_shade[k + 1]));
-      ms_shade += m; ++n_shade;
-      (void)hipEventDestroy(tm.ev_shade[k]); (void)hipEventDestroy(tm.ev_shade[k + 1]);
-    }
-    tm.ev_shade.clear();
+    wave_done(c, r, c->last_pass_waves + 1, w.off, 0, 0);
+    t0 = w.t1;
   }
-  HIPCHK(hipEventRecord(e1, s));
-  HIPCHK(hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  (void)hipEventDestroy(eb0); (void)hipEventDestroy(eb1); (void)hipEventDestroy(ef1);
+  pass.b.record(s);
+  HIPCHK(hipEventSynchronize(pass.b));
   Counters hc;
   HIPCHK(hipMemcpy(&hc, c->counters.p, sizeof hc, hipMemcpyDeviceToHost));
   std::memcpy(c->stream_bytes, hc.sb, sizeof c->stream_bytes);
   c->mis_culled = hc.mis_culled;
   if (st) {
-    std::memset(st, 0, sizeof *st);
-    st->camera_samples = samples;
-    st->rays_camera = hc.cam; st->rays_continuation = hc.cont; st->rays_mis = hc.mis; st->rays_shadow = hc.shadow;
-    st->dropped_samples = hc.dropped;
-    st->tiles = tiles.size();
-    st->ms_total = ms;
-    st->ms_bounce = ms_bounce; st->ms_film = ms_film;
-    st->bounce_launches = launches;
-    st->path_vertices = hc.vertices;
-    st->node_visits = hc.node_visits; st->tri_tests = hc.tri_tests; st->shape_tests = hc.shape_tests;
-    st->march_ticks = hc.march_ticks;
-    st->closest_node_visits = hc.c_node_visits; st->closest_tri_tests = hc.c_tri_tests;
-    st->closest_shape_tests = hc.c_shape_tests; st->closest_march_ticks = hc.c_march_ticks;
-    st->ms_closest = ms_closest; st->closest_launches = n_closest;
-    st->ms_shade = ms_shade; st->shade_launches = n_shade;
+    *st = stats_from_counters(hc, r.st, true, true);
+    st->tiles = pl.tiles.size();
+    st->ms_total = pass.elapsed_ms();
   }
   return BLING_OK;
 }
-
 
 // addTile of tile images into a device film: for each (tile list, buffer) pair, slot k of the buffer
 // holds tile k of the list (slots of this context's tile_slot); one launch over all of them
@@ -891,15 +845,10 @@ int render_fanout(bling_ctx* c, const bling_pass_params* p, float* film_dev, bli
   // merge: peers push concurrently, the primary adds after their copies
   while (c->stage.size() < (size_t)nd) c->stage.emplace_back(new DBuf<float>());
   struct Events {                      // destroyed on every exit path, after the streams drained
-    std::vector<hipEvent_t> e;
+    std::vector<Event> done;           // one per peer that copies (members go after the destructor's body)
     std::vector<hipStream_t> drain;
-    ~Events() {
-      for (hipStream_t s : drain) (void)hipStreamSynchronize(s);
-      for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x);
-    }
+    ~Events() { for (hipStream_t s : drain) (void)hipStreamSynchronize(s); }
   } ev;
-  ev.e.assign(nd, nullptr);
-  std::vector<hipEvent_t>& done = ev.e;
   for (int j = 1; j < nd; ++j) {
     bling_ctx* d = c->peers[j - 1].get();
     const size_t bytes = dtiles[j].size() * slot_floats * sizeof(float);
@@ -909,12 +858,11 @@ int render_fanout(bling_ctx* c, const bling_pass_params* p, float* film_dev, bli
     HIPCHK(hipSetDevice(d->device));
     ev.drain.push_back(d->stream);
     HIPCHK(hipMemcpyPeerAsync(c->stage[j]->p, c->device, d->pass_tiles.p, d->device, bytes, d->stream));
-    HIPCHK(hipEventCreateWithFlags(&done[j], hipEventDisableTiming));
-    HIPCHK(hipEventRecord(done[j], d->stream));
+    ev.done.emplace_back(false);
+    ev.done.back().record(d->stream);
   }
   HIPCHK(hipSetDevice(c->device));
-  for (int j = 1; j < nd; ++j)
-    if (done[j]) HIPCHK(hipStreamWaitEvent(c->stream, done[j], 0));
+  for (const Event& done : ev.done) HIPCHK(hipStreamWaitEvent(c->stream, done, 0));
   std::vector<std::pair<const std::vector<TileDesc>*, const float*>> sets;
   for (int j = 0; j < nd; ++j) sets.emplace_back(&dtiles[j], j == 0 ? c->pass_tiles.p : c->stage[j]->p);
   ev.drain.push_back(c->stream);
@@ -925,19 +873,8 @@ int render_fanout(bling_ctx* c, const bling_pass_params* p, float* film_dev, bli
   add_tiles(c, sets, film_dev);
   if (st) {
     bling_stats a = sts[0];
-    for (int j = 1; j < nd; ++j) {
-      const bling_stats& b = sts[j];
-      a.camera_samples += b.camera_samples; a.rays_camera += b.rays_camera; a.rays_continuation += b.rays_continuation;
-      a.rays_mis += b.rays_mis; a.rays_shadow += b.rays_shadow; a.dropped_samples += b.dropped_samples;
-      a.tiles += b.tiles; a.bounce_launches += b.bounce_launches; a.path_vertices += b.path_vertices;
-      a.node_visits += b.node_visits; a.tri_tests += b.tri_tests; a.shape_tests += b.shape_tests;
-      a.march_ticks += b.march_ticks;
-      // kernel times: the slowest device's (as ms_bounce / ms_film), launches counted once
-      a.ms_closest = std::max(a.ms_closest, b.ms_closest); a.ms_shade = std::max(a.ms_shade, b.ms_shade);
-      a.closest_node_visits += b.closest_node_visits; a.closest_tri_tests += b.closest_tri_tests;
-      a.closest_shape_tests += b.closest_shape_tests; a.closest_march_ticks += b.closest_march_ticks;
-      a.ms_bounce = std::max(a.ms_bounce, b.ms_bounce); a.ms_film = std::max(a.ms_film, b.ms_film);
-    }
+    // counts summed, times the slowest device's, timed launches counted once (pass_stats.h)
+    for (int j = 1; j < nd; ++j) pass_stats::stats_add(a, sts[j], pass_stats::StatsFold::Devices);
     a.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *st = a;
   }
@@ -1119,11 +1056,8 @@ static int sample_li_impl(bling_ctx* c, uint32_t seed, uint32_t pass_index, cons
     if (st) {
       Counters hc;
       HIPCHK(hipMemcpy(&hc, c->counters.p, sizeof hc, hipMemcpyDeviceToHost));
-      std::memset(st, 0, sizeof *st);
-      st->camera_samples = n;
-      st->rays_camera = hc.cam; st->rays_continuation = hc.cont; st->rays_mis = hc.mis; st->rays_shadow = hc.shadow;
-      st->dropped_samples = hc.dropped;
-      if (S.integrator == BLING_INTEGRATOR_BIDIR || S.integrator == BLING_INTEGRATOR_NORMALS) st->path_vertices = hc.vertices;
+      bling_stats samples{}; samples.camera_samples = n;
+      *st = stats_from_counters(hc, samples, S.integrator == BLING_INTEGRATOR_BIDIR || S.integrator == BLING_INTEGRATOR_NORMALS, false);
     }
     return BLING_OK;
   });
@@ -1302,16 +1236,7 @@ int bling_render(bling_ctx* c, const bling_pass_params* p, float* film_out, blin
     bling_stats one;
     const int rc = exact ? region_pass(c, pp, &one, rtiles, rimages, rsw, rsh) : bling_render_pass(c, &pp, film_out, &one);
     if (rc != BLING_OK) return rc;
-    sum.camera_samples += one.camera_samples; sum.rays_camera += one.rays_camera;
-    sum.rays_continuation += one.rays_continuation; sum.rays_mis += one.rays_mis; sum.rays_shadow += one.rays_shadow;
-    sum.dropped_samples += one.dropped_samples; sum.tiles += one.tiles; sum.ms_total += one.ms_total;
-    sum.ms_bounce += one.ms_bounce; sum.ms_film += one.ms_film; sum.bounce_launches += one.bounce_launches;
-    sum.path_vertices += one.path_vertices; sum.node_visits += one.node_visits; sum.tri_tests += one.tri_tests;
-    sum.shape_tests += one.shape_tests; sum.ms_closest += one.ms_closest; sum.closest_launches += one.closest_launches;
-    sum.march_ticks += one.march_ticks; sum.closest_node_visits += one.closest_node_visits;
-    sum.closest_tri_tests += one.closest_tri_tests; sum.closest_shape_tests += one.closest_shape_tests;
-    sum.closest_march_ticks += one.closest_march_ticks; sum.ms_shade += one.ms_shade;
-    sum.shade_launches += one.shade_launches;
+    pass_stats::stats_add(sum, one, pass_stats::StatsFold::Passes);
     if (st) *st = sum;
     if (pp.flags & BLING_PASS_REGION_EVENTS) {                     // forM_ ... RegionStarted w, SamplesAdded w img'
       const std::vector<TileDesc> tiles = exact ? rtiles : pass_tiles(c->S, pp.shard_rank, pp.shard_world, pp.tile_stride);
@@ -1483,19 +1408,15 @@ int bling_trace_device(bling_ctx* c, const void* rays, size_t n, int any_hit, vo
     if (!c || !rays || !prim_dev) throw std::invalid_argument("null argument");
     if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
     HIPCHK(hipSetDevice(c->device));
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, c->stream));
+    const EventPair ev;
+    ev.a.record(c->stream);
     for (int r = 0; r < std::max(1, repeats); ++r)
       launch_trace(c, static_cast<const float*>(rays), (uint32_t)n, any_hit, static_cast<float*>(t_dev),
                    static_cast<uint32_t*>(prim_dev), static_cast<float*>(bary_dev));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, c->stream));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (ms_out) *ms_out = ms / std::max(1, repeats);
+    ev.b.record(c->stream);
+    HIPCHK(hipEventSynchronize(ev.b));
+    if (ms_out) *ms_out = ev.elapsed_ms() / std::max(1, repeats);
     return BLING_OK;
   });
 }

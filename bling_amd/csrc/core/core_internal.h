@@ -57,6 +57,20 @@ struct DBuf {
   ~DBuf() { free(); }
 };
 
+// A HIP event, destroyed on every way out of its scope (a HIPCHK that throws included); moved, never copied.
+struct Event {
+  hipEvent_t e = nullptr;
+  explicit Event(bool timing = true) { HIPCHK(timing ? hipEventCreate(&e) : hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
+  Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+  ~Event() { if (e) (void)hipEventDestroy(e); }
+  operator hipEvent_t() const { return e; }
+  void record(hipStream_t s) const { HIPCHK(hipEventRecord(e, s)); }
+};
+inline float elapsed_ms(const Event& from, const Event& to) { float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, from, to)); return ms; }
+struct EventPair {     // the two events around something timed
+  Event a, b;
+  float elapsed_ms() const { return bcore::elapsed_ms(a, b); }
+};
 
 // device bytes per path in flight, for sizing waves: per path set the SoA streams of wavefront.h
 // PathSet (org, dir, hit, meta, mdir, fac, sh_o, sh_d: 16 B each; mhit 8 B; fm, occ, rtex 4 B each),
@@ -485,10 +499,25 @@ struct HalfWave {
   uint32_t max_tile;
 };
 
+// The event pairs of a timed pass (BLING_PASS_KERNEL_TIMING), owned: the wave drivers wrap their closest-hit
+// and shading launches in timed() (a pair on s around what fn enqueues), render() harvests after each wave's sync.
 struct WaveTiming {
+  enum Kind { Closest, Shade };      // each k_trace_closest launch; each (fused resolve +) shade launch
   bool on = false;
-  std::vector<hipEvent_t> ev;      // pairs around each k_trace_closest launch
-  std::vector<hipEvent_t> ev_shade;   // pairs around each fused resolve + shade launch
+  std::vector<EventPair> pairs[2];
+  template <class Fn>
+  void timed(Kind k, hipStream_t s, Fn&& fn) {
+    if (!on) return fn();
+    EventPair p;
+    p.a.record(s); fn(); p.b.record(s);
+    pairs[k].push_back(std::move(p));
+  }
+  // adds every pair's elapsed time and count to the pass's sums; the launches must have finished
+  void harvest(double& ms_closest, uint64_t& n_closest, double& ms_shade, uint64_t& n_shade) {
+    for (const EventPair& p : pairs[Closest]) { ms_closest += p.elapsed_ms(); ++n_closest; }
+    for (const EventPair& p : pairs[Shade]) { ms_shade += p.elapsed_ms(); ++n_shade; }
+    pairs[Closest].clear(); pairs[Shade].clear();
+  }
 };
 
 inline unsigned grid_for(uint32_t items) {

@@ -1,6 +1,6 @@
 // core_wave.h -- the per-vertex launch sequence of one wave of paths (Path and DirectLighting) and
 // batch traversal, as templates over the kernel feature profile.  Included only by the profile units
-// prof_<k>.hip, each of which instantiates one profile.
+// prof_<k>.hip, each of which instantiates one profile.  A timed pass's launches go through WaveTiming::timed.
 #pragma once
 #include "core_internal.h"
 
@@ -160,22 +160,8 @@ struct WaveRun {
       (void)anyq;
     }
   }
-  // a pair of events around the launches fn enqueues, when the pass is timed
-  template <class Fn>
-  void timed(std::vector<hipEvent_t>& ev, Fn&& fn) {
-    if (tm && tm->on) {
-      hipEvent_t a, b;
-      HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
-      ev.push_back(a); ev.push_back(b);
-      HIPCHK(hipEventRecord(a, s));
-      fn();
-      HIPCHK(hipEventRecord(b, s));
-    } else {
-      fn();
-    }
-  }
   void trace(int depth) {
-    timed(tm->ev, [&] { march(false); tl.closest(W); });   // the closest-hit queries' time includes their march
+    tm->timed(WaveTiming::Closest, s, [&] { march(false); tl.closest(W); });   // the closest-hit queries' time includes their march
     if (depth > 0) {
       march(true);
       tl.any(W);
@@ -189,7 +175,7 @@ struct WaveRun {
     // depth > 0: resolve(d - 1) + shade(d) over the resolve list of d - 1 (wavefront.h k_shade<F, true>):
     // reads the current set at the listed slots, writes vertex d to the next set at its entries;
     // depth 0 is timed with the fused launches (ms_shade)
-    timed(tm->ev_shade, [&] {
+    tm->timed(WaveTiming::Shade, s, [&] {
       if (depth > 0) shade_launch<F, true>(gs, s, d, W, depth, qin, seed, pass, C);
       else shade_launch<F, false>(gs, s, d, W, depth, qin, seed, pass, C);
     });
@@ -212,8 +198,7 @@ struct WaveRun {
 
 template <uint32_t F, bool STATS, bool ALLL>
 int run_wave_t(bling_ctx* c, WaveState W, uint32_t n, uint32_t seed, uint32_t pass, WaveTiming* tm) {
-  WaveTiming none;
-  WaveRun<F, STATS, ALLL> r(c, W, n, c->stream, seed, pass, tm ? tm : &none);
+  WaveRun<F, STATS, ALLL> r(c, W, n, c->stream, seed, pass, tm);
   for (int k = 0; k < 2 * (c->S.max_depth + 1); ++k) r.stage(k);
   return r.launches;
 }
@@ -226,9 +211,8 @@ int run_wave_t(bling_ctx* c, WaveState W, uint32_t n, uint32_t seed, uint32_t pa
 // traversal grid takes half of the co-resident blocks; the shade grid is bling_ctx::half_shade_blocks.
 template <uint32_t F, bool STATS, bool ALLL>
 int run_wave_pair_t(bling_ctx* c, const HalfWave* h, uint32_t seed, uint32_t pass, WaveTiming* tm) {
-  WaveTiming none;
-  WaveRun<F, STATS, ALLL> a(c, h[0].W, h[0].n, h[0].s, seed, pass, tm ? tm : &none, 2, c->half_shade_blocks);
-  WaveRun<F, STATS, ALLL> b(c, h[1].W, h[1].n, h[1].s, seed, pass, tm ? tm : &none, 2, c->half_shade_blocks);
+  WaveRun<F, STATS, ALLL> a(c, h[0].W, h[0].n, h[0].s, seed, pass, tm, 2, c->half_shade_blocks);
+  WaveRun<F, STATS, ALLL> b(c, h[1].W, h[1].n, h[1].s, seed, pass, tm, 2, c->half_shade_blocks);
   const int stages = 2 * (c->S.max_depth + 1);
   a.raygen(h[0]);
   a.stage(0);
@@ -257,16 +241,7 @@ int run_wave_dl_t(bling_ctx* c, WaveState W, uint32_t n, uint32_t seed, uint32_t
   uint32_t live = n;
   int launches = 0;
   for (int step = 0;; ++step) {
-    if (tm && tm->on) {
-      hipEvent_t a, b;
-      HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
-      tm->ev.push_back(a); tm->ev.push_back(b);
-      HIPCHK(hipEventRecord(a, s));
-      tl.closest(W);
-      HIPCHK(hipEventRecord(b, s));
-    } else {
-      tl.closest(W);
-    }
+    tm->timed(WaveTiming::Closest, s, [&] { tl.closest(W); });
     ++launches;
     if (step > 0) {
       tl.any(W);
@@ -297,6 +272,7 @@ int run_wave_dl_t(bling_ctx* c, WaveState W, uint32_t n, uint32_t seed, uint32_t
 
 template <uint32_t F>
 int run_wave_prof(bling_ctx* c, const WaveState& W, uint32_t n, uint32_t seed, uint32_t pass, bool stats, WaveTiming* tm) {
+  WaveTiming none; if (!tm) tm = &none;   // an untimed wave: the templates above take tm non-NULL
   const bool all = use_bvh4<F>() ? c->lds_all4 : c->lds_all;
   if (c->S.integrator == BLING_INTEGRATOR_DIRECT) {
     if (all)
@@ -310,6 +286,7 @@ int run_wave_prof(bling_ctx* c, const WaveState& W, uint32_t n, uint32_t seed, u
 
 template <uint32_t F>
 int run_wave_pair_prof(bling_ctx* c, const HalfWave* h, uint32_t seed, uint32_t pass, bool stats, WaveTiming* tm) {
+  WaveTiming none; if (!tm) tm = &none;
   const bool all = use_bvh4<F>() ? c->lds_all4 : c->lds_all;
   if (c->S.integrator == BLING_INTEGRATOR_DIRECT) throw std::runtime_error("a pipelined pass runs the Path integrator only");
   if (all)

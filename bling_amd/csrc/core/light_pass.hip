@@ -18,30 +18,26 @@ uint32_t light_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, uint32_t first
   B.rec = rec_cap > 0 ? P.rec.p : nullptr;
   B.rec_count = P.rec_count.p;
   B.rec_cap = rec_cap;
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+  const EventPair ev;
   HIPCHK(hipMemsetAsync(P.ctr.p, 0, 4 * sizeof(unsigned long long), s));
   HIPCHK(hipMemsetAsync(P.rec_count.p, 0, sizeof(uint32_t), s));
-  HIPCHK(hipEventRecord(e0, s));
+  ev.a.record(s);
   if (count > 0) {
     k_lt_photon<F><<<(unsigned)(((uint64_t)count + 255) / 256), TRACE_BLOCK, c->lds_trace, s>>>(c->dscene.p, B, first, count,
                                                                                                seed, pass);
     HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipEventRecord(e1, s));
+  ev.b.record(s);
   unsigned long long ctr[4];
   uint32_t nrec = 0;
   HIPCHK(hipMemcpyAsync(ctr, P.ctr.p, sizeof ctr, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(&nrec, P.rec_count.p, sizeof nrec, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (st) {
-    float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, e0, e1));
     st->photons = count;
     st->photon_rays = ctr[0]; st->shadow_rays = ctr[1]; st->splats = ctr[2]; st->dropped = ctr[3];
-    st->ms_total = t;
+    st->ms_total = ev.elapsed_ms();
   }
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   return nrec;
 }
 

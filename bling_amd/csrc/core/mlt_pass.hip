@@ -80,19 +80,6 @@ float mlt_boot_select(const float* I, uint32_t nboot, uint32_t seed, uint32_t pa
   return sumI / (float)nboot;
 }
 
-namespace {
-
-// the pass's two timing events, destroyed on every way out
-struct EventPair {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  EventPair() { HIPCHK(hipEventCreate(&e0)); if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); throw HipError("hipEventCreate"); } }
-  EventPair(const EventPair&) = delete;
-  EventPair& operator=(const EventPair&) = delete;
-  ~EventPair() { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
-};
-
-}  // namespace
-
 void mlt_pass_run(bling_ctx* c, uint32_t seed, uint32_t pass, bool splat, uint32_t rec_first, uint32_t rec_chains,
                   bling_mlt_stats* st, MltOut* out) {
   const bling_metropolis& mp = c->mp;
@@ -125,11 +112,10 @@ void mlt_pass_run(bling_ctx* c, uint32_t seed, uint32_t pass, bool splat, uint32
   B.wt = 1.f / mp.mpp; B.plarge = mp.plarge;
   WaveState W = c->state();
   W.Lfull = P.lfull.p;
-  const EventPair ev;
-  const hipEvent_t e0 = ev.e0, e1 = ev.e1;
+  const EventPair ev;                    // the pass's two timing events
   HIPCHK(hipMemsetAsync(P.ctr.p, 0, 4 * sizeof(unsigned long long), s));
   HIPCHK(hipMemsetAsync(c->counters.p, 0, sizeof(Counters), s));
-  HIPCHK(hipEventRecord(e0, s));
+  ev.a.record(s);
   // bootstrap (:142-169): evalI of nboot initialSamples, in chunks of the wave
   for (uint32_t first = 0; first < nboot; first += cap) {
     const uint32_t n = std::min(cap, nboot - first);
@@ -157,21 +143,19 @@ void mlt_pass_run(bling_ctx* c, uint32_t seed, uint32_t pass, bool splat, uint32
     k_mlt_accept<<<(live + 255) / 256, 256, 0, s>>>(c->dscene.p, B, P.lfull.p, live, (uint32_t)m, seed, pass);
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(e1, s));
+  ev.b.record(s);
   unsigned long long ctr[4];
   Counters hc;
   HIPCHK(hipMemcpyAsync(ctr, P.ctr.p, sizeof ctr, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(&hc, c->counters.p, sizeof hc, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (st) {
-    float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, e0, e1));
     std::memset(st, 0, sizeof *st);
     st->b = b;
     st->mutations = M; st->large_steps = ctr[0]; st->accepted = ctr[1]; st->dropped = ctr[2]; st->splats = ctr[3];
     st->rays_camera = hc.cam; st->rays_continuation = hc.cont; st->rays_mis = hc.mis; st->rays_shadow = hc.shadow;
     st->path_vertices = hc.vertices;
-    st->ms_total = t;
+    st->ms_total = ev.elapsed_ms();
   }
   if (out) {
     out->b = b;

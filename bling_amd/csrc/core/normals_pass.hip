@@ -25,19 +25,7 @@ int normals_wave_t(bling_ctx* c, WaveState W, uint32_t n, WaveTiming* tm) {
   const DevScene* d = c->dscene.p;
   Counters* C = c->counters.p;
   int launches = 0;
-  auto timed = [&](std::vector<hipEvent_t>& ev, auto&& fn) {
-    if (tm && tm->on) {
-      hipEvent_t a, b;
-      HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
-      ev.push_back(a); ev.push_back(b);
-      HIPCHK(hipEventRecord(a, s));
-      fn();
-      HIPCHK(hipEventRecord(b, s));
-    } else {
-      fn();
-    }
-  };
-  timed(tm->ev, [&] {
+  tm->timed(WaveTiming::Closest, s, [&] {     // tm is never NULL here: normals_wave_prof substitutes an empty one
     if constexpr (!(F & FT_FRACTAL)) {
       if (c->S.bf_tris + c->S.bf_shapes > 0) {
         const unsigned g = persistent_grid(k_trace_closest_bf<F, false>, 0, n);
@@ -76,7 +64,7 @@ int normals_wave_t(bling_ctx* c, WaveState W, uint32_t n, WaveTiming* tm) {
     k_trace_closest<F, false, ALLL><<<g, 256, lds, s>>>(d, W, C);
     ++launches;
   });
-  timed(tm->ev_shade, [&] { k_shade_nm<F><<<grid_for(n), 256, 0, s>>>(d, W, n, C); });
+  tm->timed(WaveTiming::Shade, s, [&] { k_shade_nm<F><<<grid_for(n), 256, 0, s>>>(d, W, n, C); });
   return launches + 1;
 }
 

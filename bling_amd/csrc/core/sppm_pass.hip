@@ -73,11 +73,9 @@ static void sppm_launch_eye(bling_ctx* c, const WaveState& W, uint32_t seed, uin
 template <uint32_t F>
 void sppm_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, bling_sppm_stats* st) {
   SppmState& P = c->sppm;
-  const DevScene& S = c->S;
   hipStream_t s = c->stream;
-  hipEvent_t e0, e1, e2, e3;
-  HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventCreate(&e2)); HIPCHK(hipEventCreate(&e3));
-  HIPCHK(hipEventRecord(e0, s));
+  const Event e0, e1, e2, e3;
+  e0.record(s);
   WaveState W{};
   W.result = P.result.p; W.img = P.img.p;
   // mkHitPoints; an overflowing hit-point buffer is grown and the (deterministic) pass re-run
@@ -90,7 +88,7 @@ void sppm_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, bling_sppm_stats* s
     sppm_launch_eye<F>(c, W, seed, pass);
   }
   k_film<<<P.n_tiles, 256, 0, s>>>(c->dscene.p, W, P.tiles.p, P.film.p, nullptr, 0, 0);
-  HIPCHK(hipEventRecord(e1, s));
+  e1.record(s);
   // mkHash: grid, bucket counts, offsets, entries
   HIPCHK(hipMemsetAsync(P.grid.p, 0, sizeof(SppmGrid), s));
   if (nhp > 0) {
@@ -109,7 +107,7 @@ void sppm_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, bling_sppm_stats* s
     k_sppm_cells<true><<<gb, 256, 0, s>>>(sppm_bufs(c));
     k_sppm_kd<<<gb, 256, 0, s>>>(sppm_bufs(c));                           // a kd-tree per bucket
   }
-  HIPCHK(hipEventRecord(e2, s));
+  e2.record(s);
   // photons (threads x sn^2, SPPM.hs:441-453, 474)
   const uint32_t sn = (uint32_t)std::max(1, (int)std::ceil(std::sqrt((float)c->cfg.sppm_photons / (float)P.nth)));
   const uint64_t nph = (uint64_t)P.nth * sn * sn;
@@ -119,20 +117,17 @@ void sppm_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, bling_sppm_stats* s
                                                                                    seed, pass);
   HIPCHK(hipGetLastError());
   k_sppm_stats<<<(P.n_stats + 255) / 256, 256, 0, s>>>(sppm_bufs(c), P.nth, c->cfg.sppm_alpha);
-  HIPCHK(hipEventRecord(e3, s));
+  e3.record(s);
   unsigned long long ctr[4];
   HIPCHK(hipMemcpyAsync(ctr, P.ctr.p, sizeof ctr, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (st) {
-    float a = 0.f, b = 0.f, t = 0.f;
-    HIPCHK(hipEventElapsedTime(&a, e0, e1)); HIPCHK(hipEventElapsedTime(&b, e1, e2)); HIPCHK(hipEventElapsedTime(&t, e0, e3));
+    const float a = elapsed_ms(e0, e1), b = elapsed_ms(e1, e2), t = elapsed_ms(e0, e3);
     st->hitpoints = std::min(nhp, P.hp_cap);
     st->photons = nph;
     st->cam_rays = ctr[0]; st->photon_rays = ctr[1]; st->photon_hits = ctr[2]; st->dropped = ctr[3];
     st->ms_eye = a; st->ms_hash = b; st->ms_photon = t - a - b; st->ms_total = t;
   }
-  for (auto e : {e0, e1, e2, e3}) (void)hipEventDestroy(e);
-  (void)S;
 }
 
 template void sppm_pass_t<kProfiles[0]>(bling_ctx*, uint32_t, uint32_t, bling_sppm_stats*);
