@@ -12,6 +12,7 @@
 #   tests/ref/_build/libnm_ref.so     CPU restatement of the normal-map integrator over the oracle (tests)
 
 HIPCC    ?= /opt/rocm/bin/hipcc
+ROCM     ?= $(patsubst %/bin/,%,$(dir $(HIPCC)))
 CXX      ?= g++
 ARCH     ?= gfx950
 LIBDIR   := bling_amd/_lib
@@ -106,8 +107,8 @@ $(LIBDIR)/libbling_hip.so: $(CORE_OBJ)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(CORE_OBJ)
 
 $(LIBDIR)/bling: bling_amd/csrc/host/bling_main.cpp $(LIBDIR)/libbling_host.so $(LIBDIR)/libbling_hip.so
-	$(CXX) -O2 -std=c++17 -o $@ bling_amd/csrc/host/bling_main.cpp -I include \
-	   -L$(LIBDIR) -lbling_host -lbling_hip -Wl,-rpath,'$$ORIGIN'
+	$(CXX) -O2 -std=c++17 -o $@ bling_amd/csrc/host/bling_main.cpp -I include -I $(ROCM)/include -D__HIP_PLATFORM_AMD__ \
+	   -L$(LIBDIR) -lbling_host -lbling_hip -L$(ROCM)/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,$(ROCM)/lib
 
 $(LIBDIR)/libbling_mathcheck.so: bling_amd/csrc/check/mathcheck.hip bling_amd/csrc/common/fast_cr.h bling_amd/csrc/common/cr_math.h
 	@mkdir -p $(LIBDIR)

@@ -108,6 +108,7 @@ class MltRecord(C.Structure):
 
 
 DEVELOP_RGB_F32, DEVELOP_RGB8, DEVELOP_RGBE = 0, 1, 2   # BLING_DEVELOP_*
+SPLAT_ORDERED = 1          # BLING_SPLAT_ORDERED
 
 
 class DevelopParams(C.Structure):
@@ -170,7 +171,7 @@ HIP_SYMBOLS = ["bling_create", "bling_scene_upload", "bling_scene_validate", "bl
                "bling_trace", "bling_trace_device", "bling_sample_li", "bling_sample_li_vertices", "bling_pass_tile_layout",
                "bling_film_add_tiles", "bling_film_add_shards", "bling_sppm_pass", "bling_sppm_pixel_stats", "bling_sppm_reset",
                "bling_render", "bling_debug_stream_bytes", "bling_debug_scene_info", "bling_debug_mis_culled", "bling_debug_set_mis_cull", "bling_debug_set_pipeline", "bling_debug_pass_results", "bling_debug_compact", "bling_debug_sppm_hitpoints", "bling_debug_sppm_buckets",
-               "bling_film_develop", "bling_film_develop_device", "bling_light_pass", "bling_debug_light_records", "bling_mlt_pass", "bling_debug_mlt_records", "bling_debug_mlt_boot", "bling_debug_mlt_set_boot", "bling_debug_bidir_terms", "bling_destroy", "bling_last_error", "bling_version"]
+               "bling_film_develop", "bling_film_develop_device", "bling_light_pass", "bling_debug_light_records", "bling_mlt_pass", "bling_debug_mlt_records", "bling_debug_mlt_boot", "bling_debug_mlt_set_boot", "bling_light_pass_device", "bling_mlt_pass_device", "bling_debug_splat_merge", "bling_debug_set_splat_budget", "bling_debug_splat_times", "bling_debug_bidir_terms", "bling_destroy", "bling_last_error", "bling_version"]
 
 
 class Progress(C.Structure):
@@ -249,6 +250,19 @@ def hip() -> C.CDLL:
             lib.bling_debug_mlt_boot.restype = C.c_int
             lib.bling_debug_mlt_set_boot.argtypes = [C.c_void_p, c_f32p, C.c_uint32]
             lib.bling_debug_mlt_set_boot.restype = C.c_int
+        if hasattr(lib, "bling_light_pass_device"):   # older experiment builds lack the device splat images
+            lib.bling_light_pass_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                    C.POINTER(LightStats)]
+            lib.bling_light_pass_device.restype = C.c_int
+            lib.bling_mlt_pass_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                  C.POINTER(MltStats)]
+            lib.bling_mlt_pass_device.restype = C.c_int
+            lib.bling_debug_splat_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+            lib.bling_debug_splat_merge.restype = C.c_int
+            lib.bling_debug_set_splat_budget.argtypes = [C.c_void_p, C.c_size_t]
+            lib.bling_debug_set_splat_budget.restype = C.c_int
+            lib.bling_debug_splat_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+            lib.bling_debug_splat_times.restype = C.c_int
         if hasattr(lib, "bling_debug_bidir_terms"):   # older experiment builds lack it
             lib.bling_debug_bidir_terms.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.c_size_t,
                                                     c_f32p, C.POINTER(C.c_int32)]

@@ -533,6 +533,7 @@ void upload_scene(bling_ctx* c, const bling_scene_desc* d) {
   c->sppm.free_all();
   c->light.free_all();
   c->mlt.free_all();
+  c->merge.free_all();                   // the record budget stays: it belongs to the context
   c->mlt_boot_override.clear();
 }
 
@@ -1527,7 +1528,7 @@ static int light_ready(bling_ctx* c) {
   return BLING_OK;
 }
 
-static uint32_t light_launch(bling_ctx* c, uint32_t seed, uint32_t pass, uint32_t first, uint32_t count, bool splat,
+static uint32_t light_launch(bling_ctx* c, uint32_t seed, uint32_t pass, uint32_t first, uint32_t count, float* splat,
                              uint32_t rec_cap, bling_light_stats* st) {
   if ((c->features & ~kProfiles[0]) == 0u) return light_pass_t<kProfiles[0]>(c, seed, pass, first, count, splat, rec_cap, st);
   return light_pass_t<kSppmAll>(c, seed, pass, first, count, splat, rec_cap, st);
@@ -1544,7 +1545,7 @@ int bling_light_pass(bling_ctx* c, uint32_t seed, uint32_t pass_index, float* sp
     if (splat_inout) HIPCHK(hipMemcpy(P.splat.p, splat_inout, ns * sizeof(float), hipMemcpyHostToDevice));
     else HIPCHK(hipMemset(P.splat.p, 0, ns * sizeof(float)));
     if (st) std::memset(st, 0, sizeof *st);
-    light_launch(c, seed, pass_index, 0u, (uint32_t)c->lt.pass_photons, true, 0u, st);
+    light_launch(c, seed, pass_index, 0u, (uint32_t)c->lt.pass_photons, P.splat.p, 0u, st);
     if (splat_inout) HIPCHK(hipMemcpy(splat_inout, P.splat.p, ns * sizeof(float), hipMemcpyDeviceToHost));
     return BLING_OK;
   });
@@ -1562,7 +1563,7 @@ int bling_debug_light_records(bling_ctx* c, uint32_t seed, uint32_t pass_index, 
     HIPCHK(hipSetDevice(c->device));
     // a launch needs a buffer to claim slots in: one record at least, so the count is always known
     const uint32_t rcap = (uint32_t)std::max<size_t>(cap, 1);
-    const uint32_t got = light_launch(c, seed, pass_index, first_photon, n_photons, false, rcap, nullptr);
+    const uint32_t got = light_launch(c, seed, pass_index, first_photon, n_photons, nullptr, rcap, nullptr);
     *n = got;
     if (got > cap) {
       g_err = "light records: " + std::to_string(got) + " records exceed the capacity " + std::to_string(cap);
@@ -1596,7 +1597,7 @@ int bling_mlt_pass(bling_ctx* c, uint32_t seed, uint32_t pass_index, float* spla
     if (splat_inout) HIPCHK(hipMemcpy(P.splat.p, splat_inout, ns * sizeof(float), hipMemcpyHostToDevice));
     else HIPCHK(hipMemset(P.splat.p, 0, ns * sizeof(float)));
     if (st) std::memset(st, 0, sizeof *st);
-    mlt_pass_run(c, seed, pass_index, true, 0u, 0u, st, nullptr);
+    mlt_pass_run(c, seed, pass_index, P.splat.p, false, 0u, 0u, st, nullptr);
     if (splat_inout) HIPCHK(hipMemcpy(splat_inout, P.splat.p, ns * sizeof(float), hipMemcpyDeviceToHost));
     return BLING_OK;
   });
@@ -1621,7 +1622,7 @@ int bling_debug_mlt_records(bling_ctx* c, uint32_t seed, uint32_t pass_index, ui
     }
     HIPCHK(hipSetDevice(c->device));
     MltOut out;
-    mlt_pass_run(c, seed, pass_index, false, first_chain, n_chains, nullptr, &out);
+    mlt_pass_run(c, seed, pass_index, nullptr, false, first_chain, n_chains, nullptr, &out);
     if (out.rec.size() != need) throw std::runtime_error("mlt records: count mismatch");
     if (need) std::memcpy(records, out.rec.data(), need * sizeof(bling_mlt_record));
     if (starts) std::memcpy(starts, out.start.data() + first_chain, (size_t)n_chains * sizeof(uint32_t));
@@ -1643,6 +1644,123 @@ int bling_debug_mlt_set_boot(bling_ctx* c, const float* I, uint32_t n) {
   return guarded([&] {
     if (!c || (n && !I)) throw std::invalid_argument("null argument");
     c->mlt_boot_override.assign(I, I + n);
+    return BLING_OK;
+  });
+}
+
+// ---- ordered splat films and caller-owned device splat images (splat_merge.h)
+static void splat_device_args(uint32_t flags, const void* splat_device) {
+  if (flags & ~BLING_SPLAT_ORDERED) throw std::invalid_argument("unknown splat flag bits " + std::to_string(flags & ~BLING_SPLAT_ORDERED));
+  if (!splat_device) throw std::invalid_argument("null splat_device");
+}
+
+// The ordered light tracer pass: k_lt_photon in record mode over ascending photon ranges, each merged before
+// the next.  A range whose records exceed the buffer is run again with a buffer that holds them, or, beyond
+// the budget, as two halves; nothing of it is merged before it fits.
+static int light_pass_ordered(bling_ctx* c, uint32_t seed, uint32_t pass, float* img, bling_light_stats* st) {
+  const uint32_t total = (uint32_t)c->lt.pass_photons;
+  const size_t budget = std::min<size_t>(splat_budget(c), 0x7FFFFFFFull);
+  uint32_t cap = (uint32_t)std::min<size_t>(budget, std::max<size_t>(c->light.rec.n / 2, (size_t)4 * total + 1024));
+  bling_light_stats sum{};
+  std::vector<EventPair> merges;
+  double ms_kernel = 0.;
+  uint32_t first = 0, len = total;
+  while (first < total) {
+    const uint32_t count = std::min(len, total - first);
+    bling_light_stats one{};
+    const uint32_t got = light_launch(c, seed, pass, first, count, nullptr, cap, &one);
+    ms_kernel += one.ms_total;
+    if (got > cap) {
+      if ((size_t)got <= budget) { cap = got; continue; }              // the same range, into a buffer that holds it
+      if (count == 1) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        g_err = "light tracer: photon " + std::to_string(first) + " alone writes " + std::to_string(got) +
+                " splat records, more than the record budget " + std::to_string(budget);
+        return BLING_EINVAL;
+      }
+      len = (count + 1) / 2;
+      continue;
+    }
+    merges.emplace_back();
+    merges.back().a.record(c->stream);
+    splat_merge(c, c->light.rec.p, got, SM_LAYOUT_LIGHT, img);
+    merges.back().b.record(c->stream);
+    sum.photon_rays += one.photon_rays; sum.shadow_rays += one.shadow_rays; sum.splats += one.splats; sum.dropped += one.dropped;
+    first += count;
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  double ms_merge = 0.;
+  for (const EventPair& p : merges) ms_merge += p.elapsed_ms();
+  c->merge.ms_kernel = ms_kernel; c->merge.ms_merge = ms_merge;
+  if (st) {
+    *st = sum;
+    st->photons = total;
+    st->ms_total = ms_kernel + ms_merge;
+  }
+  return BLING_OK;
+}
+
+int bling_light_pass_device(bling_ctx* c, uint32_t seed, uint32_t pass_index, uint32_t flags, void* splat_device,
+                            bling_light_stats* st) {
+  return guarded([&] {
+    if (!c) throw std::invalid_argument("null argument");
+    splat_device_args(flags, splat_device);
+    if (int rc = light_ready(c)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    if (st) std::memset(st, 0, sizeof *st);
+    float* img = static_cast<float*>(splat_device);
+    if (flags & BLING_SPLAT_ORDERED) return light_pass_ordered(c, seed, pass_index, img, st);
+    light_launch(c, seed, pass_index, 0u, (uint32_t)c->lt.pass_photons, img, 0u, st);
+    return (int)BLING_OK;
+  });
+}
+
+int bling_mlt_pass_device(bling_ctx* c, uint32_t seed, uint32_t pass_index, uint32_t flags, void* splat_device,
+                          bling_mlt_stats* st) {
+  return guarded([&] {
+    if (!c) throw std::invalid_argument("null argument");
+    splat_device_args(flags, splat_device);
+    if (int rc = mlt_ready(c)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    if (st) std::memset(st, 0, sizeof *st);
+    mlt_pass_run(c, seed, pass_index, static_cast<float*>(splat_device), (flags & BLING_SPLAT_ORDERED) != 0u, 0u, 0u, st, nullptr);
+    return BLING_OK;
+  });
+}
+
+int bling_debug_splat_merge(bling_ctx* c, const bling_splat_rec* recs, size_t n, void* splat_device) {
+  return guarded([&] {
+    if (!c || !splat_device || (n && !recs)) throw std::invalid_argument("null argument");
+    if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
+    if (n > 0x7FFFFFFFull) throw std::invalid_argument("splat merge: more than 2^31 - 1 records");
+    const size_t npix = (size_t)c->S.width * c->S.height;
+    for (size_t i = 0; i < n; ++i)
+      if (recs[i].pixel >= npix) throw std::invalid_argument("splat merge: record " + std::to_string(i) + " names pixel " +
+                                                             std::to_string(recs[i].pixel) + " of " + std::to_string(npix));
+    if (n == 0) return BLING_OK;
+    HIPCHK(hipSetDevice(c->device));
+    static_assert(sizeof(bling_splat_rec) == 2 * sizeof(uint4), "record layout");
+    MergeState& G = c->merge;
+    if (G.rec.n < 2 * n) G.rec.alloc(2 * n);
+    HIPCHK(hipMemcpyAsync(G.rec.p, recs, n * sizeof(bling_splat_rec), hipMemcpyHostToDevice, c->stream));
+    splat_merge(c, G.rec.p, n, SM_LAYOUT_SPLAT, static_cast<float*>(splat_device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return BLING_OK;
+  });
+}
+
+int bling_debug_set_splat_budget(bling_ctx* c, size_t max_records) {
+  return guarded([&] {
+    if (!c) throw std::invalid_argument("null argument");
+    c->merge.budget = max_records;
+    return BLING_OK;
+  });
+}
+
+int bling_debug_splat_times(bling_ctx* c, double* ms_kernel, double* ms_merge) {
+  return guarded([&] {
+    if (!c || !ms_kernel || !ms_merge) throw std::invalid_argument("null argument");
+    *ms_kernel = c->merge.ms_kernel; *ms_merge = c->merge.ms_merge;
     return BLING_OK;
   });
 }

@@ -23,6 +23,7 @@
 #include "light_tracer.h"
 #include "bidir.h"
 #include "mlt.h"
+#include "splat_merge.h"
 
 namespace bcore {
 using namespace bd;
@@ -156,10 +157,30 @@ struct MltState {
   }
 };
 
+// Ordered splat merge state (splat_merge.h): the per-pixel counts, segment starts, the scan's block sums,
+// the list of long segments, the segments' keys and values, the record buffer the ordered Metropolis pass
+// and bling_debug_splat_merge fill, and the record budget (0: the default, from the device's memory)
+struct MergeState {
+  DBuf<uint32_t> cnt, start, sums, longs, rec_count;
+  DBuf<unsigned long long> key;
+  DBuf<float4> val;
+  DBuf<uint4> rec;
+  size_t budget = 0, default_budget = 0;
+  double ms_kernel = 0., ms_merge = 0.;   // the last ordered pass: its photon / chain launches, its merges
+  void free_all() {
+    for (auto* b : {&cnt, &start, &sums, &longs, &rec_count}) b->free();
+    key.free(); val.free(); rec.free();
+  }
+};
+
 }  // namespace bcore
 
 struct bling_ctx;
 namespace bcore {
+// splat_merge.hip: the record budget of this context's ordered passes; the ordered merge of n records
+// (layout SM_LAYOUT_*) into the device image img (W * H * 3), enqueued on the context's stream
+size_t splat_budget(bling_ctx* c);
+void splat_merge(bling_ctx* c, const uint4* recs, size_t n, int layout, float* img);
 // film_develop.hip: bytes per pixel of a BLING_DEVELOP_* format; the window clipped to the uploaded
 // scene's image (false: empty); the threshold table's upload; one develop launch on the context's stream
 size_t develop_pixel_bytes(int format);
@@ -288,6 +309,7 @@ struct bling_ctx {
   DBuf<float> pass_tiles;          // this device's tile images of the pass (BLING_PASS_TILE_IMAGES)
   DBuf<TileSrc> tile_src;          // the merge's per-tile sources (k_add_tiles)
   std::vector<std::unique_ptr<DBuf<float>>> stage;  // primary: landing buffer of peer j's tile images
+  MergeState merge;                // the ordered splat merge (splat_merge.h)
 
   ~bling_ctx() {
     peers.clear();                          // each peer frees its memory on its own device
@@ -460,10 +482,12 @@ struct MltOut {
   std::vector<uint32_t> start;
   std::vector<bling_mlt_record> rec;
 };
-// One pass of the Metropolis renderer; splat: into the context's light.splat image; records of chains
+// One pass of the Metropolis renderer; splat: the device image it accumulates into (nullptr = none), with
+// float atomics or, ordered, through splat records and one splat_merge; records of chains
 // rec_first .. rec_first + rec_chains - 1 (0 = off).  Throws std::invalid_argument where the reference
-// would stop with an error (bootstrap selection on an unwritten slot).
-void mlt_pass_run(bling_ctx* c, uint32_t seed, uint32_t pass, bool splat, uint32_t rec_first, uint32_t rec_chains,
+// would stop with an error (bootstrap selection on an unwritten slot) and, ordered, when the pass's 2 M
+// possible splat records exceed the record budget (before any launch).
+void mlt_pass_run(bling_ctx* c, uint32_t seed, uint32_t pass, float* splat, bool ordered, uint32_t rec_first, uint32_t rec_chains,
                   bling_mlt_stats* st, MltOut* out);
 // The host bookkeeping of bootstrap (mlt_pass.hip): b' and the chains' start samples from the I values.
 float mlt_boot_select(const float* I, uint32_t nboot, uint32_t seed, uint32_t pass, uint32_t chains, uint32_t* start);
@@ -553,10 +577,10 @@ template <uint32_t F>
 void sppm_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, bling_sppm_stats* st);
 void sppm_init(bling_ctx* c);
 // One light tracer launch (light_pass.hip): photons first .. first + count - 1 of the pass into the
-// context's splat image (splat = true) and / or its record buffer of rec_cap records (0 = off);
+// device image splat (nullptr = none) and / or the context's record buffer of rec_cap records (0 = off);
 // returns the records claimed, which may exceed rec_cap.
 template <uint32_t F>
-uint32_t light_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, uint32_t first, uint32_t count, bool splat,
+uint32_t light_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, uint32_t first, uint32_t count, float* splat,
                       uint32_t rec_cap, bling_light_stats* st);
 // One wave of the bidirectional integrator (bidir_pass.hip): the n camera samples of the tile table
 // (tiles != nullptr, the largest tile of max_tile samples) or of the device list of (x, y, n) triples,

@@ -5,7 +5,7 @@
 namespace bcore {
 
 template <uint32_t F>
-uint32_t light_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, uint32_t first, uint32_t count, bool splat,
+uint32_t light_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, uint32_t first, uint32_t count, float* splat,
                       uint32_t rec_cap, bling_light_stats* st) {
   LightState& P = c->light;
   hipStream_t s = c->stream;
@@ -13,7 +13,7 @@ uint32_t light_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, uint32_t first
   if (P.rec_count.n != 1) P.rec_count.alloc(1);
   if (rec_cap > 0 && P.rec.n < (size_t)2 * rec_cap) P.rec.alloc((size_t)2 * rec_cap);
   LtBufs B{};
-  B.splat = splat ? P.splat.p : nullptr;
+  B.splat = splat;
   B.ctr = P.ctr.p;
   B.rec = rec_cap > 0 ? P.rec.p : nullptr;
   B.rec_count = P.rec_count.p;
@@ -41,9 +41,9 @@ uint32_t light_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, uint32_t first
   return nrec;
 }
 
-template uint32_t light_pass_t<kProfiles[0]>(bling_ctx*, uint32_t, uint32_t, uint32_t, uint32_t, bool, uint32_t,
+template uint32_t light_pass_t<kProfiles[0]>(bling_ctx*, uint32_t, uint32_t, uint32_t, uint32_t, float*, uint32_t,
                                              bling_light_stats*);
-template uint32_t light_pass_t<kSppmAll>(bling_ctx*, uint32_t, uint32_t, uint32_t, uint32_t, bool, uint32_t,
+template uint32_t light_pass_t<kSppmAll>(bling_ctx*, uint32_t, uint32_t, uint32_t, uint32_t, float*, uint32_t,
                                          bling_light_stats*);
 
 }  // namespace bcore

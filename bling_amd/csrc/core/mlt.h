@@ -6,7 +6,8 @@
 //   k_mlt_walk      bidir.h's two subpaths per chain, the sample values read from a primary sample
 //   k_bd_connect, k_bd_finish   unchanged (they draw nothing)
 //   k_mlt_accept    evalI (:241-242), a = min 1 (iProp / iCurr), the two guarded splats (:96-104) as
-//                   float atomics, the acceptance (:106-110) and the optional record
+//                   float atomics or as splat records for the ordered merge (MltBufs::srec, splat_merge.h),
+//                   the acceptance (:106-110) and the optional record
 // Bootstrap samples (:142-169) and each chain's first evaluation (:84) go through the same walk
 // (k_mlt_fill writes their vectors).  A primary sample is n1d + 2 n2d + 4 floats -- v1d, v2d, then the
 // camera sample's x, y, lu, lv -- stored [value][chain], so a wave's loads and stores are contiguous.
@@ -18,6 +19,7 @@
 // the draw in the reference's order (rnd2D = two draws).
 #pragma once
 #include "bidir.h"
+#include "splat_merge.h"
 
 namespace bd {
 
@@ -47,6 +49,10 @@ struct MltBufs {
   unsigned long long* ctr;   // [0] large steps, [1] accepted, [2] dropped splats, [3] splats
   uint4* rec;                // record mode: 2 uint4 per (chain, mutation) of chains rec_first ..; nullptr = off
   uint32_t rec_first, rec_chains;
+  uint4* srec;               // ordered mode: 2 uint4 per splat (splat_merge.h SM_LAYOUT_SPLAT), key = chain << 32 |
+                             // mutation << 1 | proposal; nullptr = off
+  uint32_t* srec_count;      // slots claimed
+  uint32_t srec_cap;
   uint32_t cap;
   int n1d, n2d;
   float sx, sy;              // the image size (mutate's imgSize)
@@ -162,8 +168,8 @@ static __global__ __launch_bounds__(256) void k_mlt_adopt(MltBufs B, const float
 }
 
 // splat (:68-69) then splatSample (Image.hs:201-221): outside the image first, then the NaN / infinite filter
-DEV void mlt_splat(const DevScene& S, const MltBufs& B, float x, float y, const Sp& s, unsigned long long& splats,
-                   unsigned long long& dropped) {
+DEV void mlt_splat(const DevScene& S, const MltBufs& B, float x, float y, const Sp& s, unsigned long long key,
+                   unsigned long long& splats, unsigned long long& dropped) {
   const float fx = floorf(x), fy = floorf(y);
   if (!(fx >= 0.f && fy >= 0.f && fx < (float)S.width && fy < (float)S.height)) return;
   if (s_bad(s)) { ++dropped; return; }
@@ -173,6 +179,10 @@ DEV void mlt_splat(const DevScene& S, const MltBufs& B, float x, float y, const 
   if (B.splat) {
     float* o = B.splat + 3 * ((size_t)(int)fy * S.width + (int)fx);
     atomicAdd(&o[0], X); atomicAdd(&o[1], Y); atomicAdd(&o[2], Z);
+  }
+  if (B.srec) {
+    const uint32_t slot = atomicAdd(B.srec_count, 1u);
+    if (slot < B.srec_cap) sm_write_rec(B.srec, slot, (uint32_t)(int)fy * (uint32_t)S.width + (uint32_t)(int)fx, key, X, Y, Z);
   }
 }
 
@@ -194,8 +204,9 @@ static __global__ __launch_bounds__(256) void k_mlt_accept(const DevScene* __res
     const float iProp = sY(lp), iCurr = sY(lc);
     const float q = iProp / iCurr;
     const float a = 1.f <= q ? 1.f : q;                                // GHC's min 1 q: NaN stays NaN
-    if (iCurr > 0.f && !__builtin_isinf(1.f / iCurr)) mlt_splat(S, B, xc, yc, sscale(lc, (1.f - a) / iCurr * B.wt), splats, dropped);
-    if (iProp > 0.f && !__builtin_isinf(1.f / iProp)) mlt_splat(S, B, xp, yp, sscale(lp, a / iProp * B.wt), splats, dropped);
+    const unsigned long long okey = ((unsigned long long)c << 32) | ((unsigned long long)m << 1);   // the current sample first
+    if (iCurr > 0.f && !__builtin_isinf(1.f / iCurr)) mlt_splat(S, B, xc, yc, sscale(lc, (1.f - a) / iCurr * B.wt), okey, splats, dropped);
+    if (iProp > 0.f && !__builtin_isinf(1.f / iProp)) mlt_splat(S, B, xp, yp, sscale(lp, a / iProp * B.wt), okey | 1ull, splats, dropped);
     const uint32_t fl = B.flags[c];
     const SampleKey k = sample_key(seed, pass, MLT_CHAIN_PIXEL | c, m);
     const float r = draw01(k, brng::DIM_FRESH1D + (fl >> 1));

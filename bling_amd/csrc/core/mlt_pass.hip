@@ -80,7 +80,7 @@ float mlt_boot_select(const float* I, uint32_t nboot, uint32_t seed, uint32_t pa
   return sumI / (float)nboot;
 }
 
-void mlt_pass_run(bling_ctx* c, uint32_t seed, uint32_t pass, bool splat, uint32_t rec_first, uint32_t rec_chains,
+void mlt_pass_run(bling_ctx* c, uint32_t seed, uint32_t pass, float* splat, bool ordered, uint32_t rec_first, uint32_t rec_chains,
                   bling_mlt_stats* st, MltOut* out) {
   const bling_metropolis& mp = c->mp;
   const DevScene& S = c->S;
@@ -89,6 +89,12 @@ void mlt_pass_run(bling_ctx* c, uint32_t seed, uint32_t pass, bool splat, uint32
   const uint32_t C = (uint32_t)mp.chains, nboot = (uint32_t)mp.bootstrap;
   const uint64_t per = M / C, extra = M % C;
   const uint64_t nsteps = per + (extra ? 1 : 0);
+  ordered = ordered && splat;
+  // ordered: the order is chain-major, the launches are mutation-major, so every splat of the pass (two a
+  // mutation at most) is recorded and merged once
+  if (ordered && 2 * M > (uint64_t)splat_budget(c))
+    throw std::invalid_argument("metropolis: an ordered pass may write 2 M = " + std::to_string(2 * M) +
+                                " splat records, more than the record budget " + std::to_string(splat_budget(c)));
   // the wave: every chain, and bootstrap chunks of at most kMltBootChunk samples
   const uint32_t wave = std::max(C, std::min(nboot, kMltBootChunk));
   const uint32_t cap = (wave + 255u) & ~255u;
@@ -103,7 +109,14 @@ void mlt_pass_run(bling_ctx* c, uint32_t seed, uint32_t pass, bool splat, uint32
   if (nrec && P.rec.n < 2 * nrec) P.rec.alloc(2 * nrec);
   MltBufs B{};
   B.cur = P.cur.p; B.prop = P.prop.p; B.cur_l = P.cur_l.p; B.flags = P.flags.p;
-  B.splat = splat ? c->light.splat.p : nullptr;
+  B.splat = ordered ? nullptr : splat;
+  MergeState& G = c->merge;
+  if (ordered) {
+    if (G.rec.n < (size_t)4 * M) G.rec.alloc((size_t)4 * M);
+    if (G.rec_count.n != 1) G.rec_count.alloc(1);
+    B.srec = G.rec.p; B.srec_count = G.rec_count.p; B.srec_cap = (uint32_t)(2 * M);
+    HIPCHK(hipMemsetAsync(G.rec_count.p, 0, sizeof(uint32_t), s));
+  }
   B.ctr = P.ctr.p;
   B.rec = nrec ? P.rec.p : nullptr;
   B.rec_first = rec_first; B.rec_chains = rec_chains;
@@ -143,6 +156,16 @@ void mlt_pass_run(bling_ctx* c, uint32_t seed, uint32_t pass, bool splat, uint32
     k_mlt_accept<<<(live + 255) / 256, 256, 0, s>>>(c->dscene.p, B, P.lfull.p, live, (uint32_t)m, seed, pass);
   }
   HIPCHK(hipGetLastError());
+  const EventPair evm;                   // the ordered merge's share of the pass
+  if (ordered) {
+    uint32_t nsplat = 0;
+    HIPCHK(hipMemcpyAsync(&nsplat, G.rec_count.p, sizeof nsplat, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (nsplat > B.srec_cap) throw std::runtime_error("metropolis: splat record count beyond 2 M");
+    evm.a.record(s);
+    splat_merge(c, G.rec.p, nsplat, SM_LAYOUT_SPLAT, splat);
+    evm.b.record(s);
+  }
   ev.b.record(s);
   unsigned long long ctr[4];
   Counters hc;
@@ -157,6 +180,7 @@ void mlt_pass_run(bling_ctx* c, uint32_t seed, uint32_t pass, bool splat, uint32
     st->path_vertices = hc.vertices;
     st->ms_total = ev.elapsed_ms();
   }
+  if (ordered) { G.ms_merge = evm.elapsed_ms(); G.ms_kernel = ev.elapsed_ms() - G.ms_merge; }
   if (out) {
     out->b = b;
     out->start = start;

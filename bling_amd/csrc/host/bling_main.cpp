@@ -3,9 +3,14 @@
 // pass-NNNNN.png and .hdr at PassDone) over the host loader and the MI355X core.
 //
 //   bling <scene.bling> [--overrides "image=W,H;..."] [--passes N] [--out prefix] [--device D]
-//         [--develop host|device]
+//         [--develop host|device] [--splat atomic|ordered]
 // --develop device makes each written pass's 8-bit and RGBE pixels on the device (bling_film_develop)
 // and hands them to the encoders; the default, host, develops with the host library.  Same files.
+// --splat ordered (light tracer and Metropolis scenes) adds every pixel's splats in the reference's order
+// (BLING_SPLAT_ORDERED): the same files on every run; the default, atomic, adds them with float atomics.
+// With --develop device, or --splat ordered, such a scene's splat image lives on the device for the whole
+// run (bling_light_pass_device / bling_mlt_pass_device); --develop device then develops it there
+// (bling_film_develop_device) and only the developed pixels come back.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -13,10 +18,54 @@
 #include <string>
 #include <vector>
 
+#include <hip/hip_runtime_api.h>
+
 #include "bling.h"
 #include "bling_host.h"
 
 namespace {
+// The device buffers of a light tracer / Metropolis run whose splat image stays on the device: the image,
+// an empty film and the developed pixels (4 bytes a pixel at most).
+struct DeviceFilm {
+  void *splat = nullptr, *film = nullptr, *out = nullptr;
+  bool alloc(int w, int h) {
+    const size_t px = (size_t)w * h;
+    if (hipMalloc(&splat, px * 12) != hipSuccess || hipMalloc(&film, px * 16) != hipSuccess || hipMalloc(&out, px * 4) != hipSuccess ||
+        hipMemset(splat, 0, px * 12) != hipSuccess || hipMemset(film, 0, px * 16) != hipSuccess) {
+      std::fprintf(stderr, "device film: %s\n", hipGetErrorString(hipGetLastError()));
+      return false;
+    }
+    return true;
+  }
+  ~DeviceFilm() { (void)hipFree(splat); (void)hipFree(film); (void)hipFree(out); }
+};
+
+// One written pass of a device splat image: developed on the device, or fetched and developed by the host library.
+int write_pass(bling_ctx* ctx, bool on_device, const std::string& name, const float* film, const float* splat, float sw,
+               int w, int h, std::vector<float>& rgb);
+int write_pass_device_film(bling_ctx* ctx, bool dev_develop, const DeviceFilm& df, const std::string& name, const float* film,
+                           float sw, int w, int h, std::vector<float>& rgb) {
+  const size_t px = (size_t)w * h;
+  if (!dev_develop) {
+    std::vector<float> splat(px * 3);
+    if (hipMemcpy(splat.data(), df.splat, px * 12, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "splat image: copy failed\n"); return 1; }
+    return write_pass(ctx, false, name, film, splat.data(), sw, w, h, rgb);
+  }
+  std::vector<unsigned char> px8(px * 3), pxe(px * 4);
+  bling_develop_params dp{BLING_DEVELOP_RGB8, sw, {0, w - 1, 0, h - 1}};
+  if (bling_film_develop_device(ctx, &dp, df.film, df.splat, df.out) != 0) { std::fprintf(stderr, "%s\n", bling_last_error()); return 1; }
+  if (hipMemcpy(px8.data(), df.out, px * 3, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "developed image: copy failed\n"); return 1; }
+  dp.format = BLING_DEVELOP_RGBE;
+  if (bling_film_develop_device(ctx, &dp, df.film, df.splat, df.out) != 0) { std::fprintf(stderr, "%s\n", bling_last_error()); return 1; }
+  if (hipMemcpy(pxe.data(), df.out, px * 4, hipMemcpyDeviceToHost) != hipSuccess) { std::fprintf(stderr, "developed image: copy failed\n"); return 1; }
+  const std::string png = name + ".png", hdr = name + ".hdr";
+  if (bling_host_write_png_rgb8(png.c_str(), px8.data(), w, h) != 0 || bling_host_write_hdr_rgbe(hdr.c_str(), pxe.data(), w, h) != 0) {
+    std::fprintf(stderr, "%s\n", bling_host_last_error());
+    return 1;
+  }
+  return 0;
+}
+
 // One written pass: <name>.png and <name>.hdr.  On the device: RGB8 and RGBE through bling_film_develop
 // and the two pixel encoders; on the host: today's path.  splat may be NULL (then sw is unused).
 int write_pass(bling_ctx* ctx, bool on_device, const std::string& name, const float* film, const float* splat, float sw,
@@ -52,14 +101,14 @@ int write_pass(bling_ctx* ctx, bool on_device, const std::string& name, const fl
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    std::fprintf(stderr, "usage: %s scene.bling [--overrides S] [--passes N] [--out prefix] [--device D] [--develop host|device]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s scene.bling [--overrides S] [--passes N] [--out prefix] [--device D] [--develop host|device] [--splat atomic|ordered]\n", argv[0]);
     return 2;
   }
   const char* scene = argv[1];
   const char* ov = nullptr;
   const char* out = "pass";
   int passes = 1, device = 0;
-  bool dev_develop = false;
+  bool dev_develop = false, ordered = false;
   for (int i = 2; i + 1 < argc; i += 2) {
     if (!std::strcmp(argv[i], "--overrides")) ov = argv[i + 1];
     else if (!std::strcmp(argv[i], "--passes")) passes = std::atoi(argv[i + 1]);
@@ -71,6 +120,12 @@ int main(int argc, char** argv) {
         return 2;
       }
       dev_develop = !std::strcmp(argv[i + 1], "device");
+    } else if (!std::strcmp(argv[i], "--splat")) {
+      if (std::strcmp(argv[i + 1], "atomic") && std::strcmp(argv[i + 1], "ordered")) {
+        std::fprintf(stderr, "--splat takes atomic or ordered, not %s\n", argv[i + 1]);
+        return 2;
+      }
+      ordered = !std::strcmp(argv[i + 1], "ordered");
     }
   }
   bling_host_scene* hs = nullptr;
@@ -84,20 +139,28 @@ int main(int argc, char** argv) {
   }
   int w = d->config.width, h = d->config.height;
   std::vector<float> film((size_t)w * h * 4, 0.f), rgb((size_t)w * h * 3);
+  const bool splats = d->config.renderer == BLING_RENDERER_LIGHT || d->config.renderer == BLING_RENDERER_METROPOLIS;
+  const bool device_film = splats && (dev_develop || ordered);
+  const uint32_t splat_flags = ordered ? BLING_SPLAT_ORDERED : 0u;
+  DeviceFilm df;
+  if (device_film && (hipSetDevice(device) != hipSuccess || !df.alloc(w, h))) return 1;
   if (d->config.renderer == BLING_RENDERER_LIGHT) {
     // instance Renderer LightTracer (Renderer/LightTracer.hs:37-52): the film stays empty, every pass
     // adds its splats, and the image of pass n weighs them with 1 / (n * passPhotons)
     std::vector<float> splat((size_t)w * h * 3, 0.f);
     for (int p = 1; p <= passes; ++p) {
       bling_light_stats st;
-      if (bling_light_pass(ctx, 0x0B11A6u, (uint32_t)p, splat.data(), &st) != 0) { std::fprintf(stderr, "%s\n", bling_last_error()); return 1; }
+      const int rc = device_film ? bling_light_pass_device(ctx, 0x0B11A6u, (uint32_t)p, splat_flags, df.splat, &st)
+                                 : bling_light_pass(ctx, 0x0B11A6u, (uint32_t)p, splat.data(), &st);
+      if (rc != 0) { std::fprintf(stderr, "%s\n", bling_last_error()); return 1; }
       std::printf("pass %d: %.1f ms, %llu photons, %llu splats, %.1f Mrays/s\n", p, st.ms_total, (unsigned long long)st.photons,
                   (unsigned long long)st.splats, (st.photon_rays + st.shadow_rays) / (st.ms_total * 1e3));
       const float sw = 1.f / (float)((long long)p * d->light.pass_photons);
       char name[512];
       std::snprintf(name, sizeof name, "%s-%05d", out, p);
       std::printf("Writing %s...\n", name);
-      if (write_pass(ctx, dev_develop, name, film.data(), splat.data(), sw, w, h, rgb) != 0) return 1;
+      if ((device_film ? write_pass_device_film(ctx, dev_develop, df, name, film.data(), sw, w, h, rgb)
+                       : write_pass(ctx, dev_develop, name, film.data(), splat.data(), sw, w, h, rgb)) != 0) return 1;
     }
     bling_destroy(ctx);
     bling_host_free(hs);
@@ -110,7 +173,9 @@ int main(int argc, char** argv) {
     float b = 1.f;
     for (int p = 1; p <= passes; ++p) {
       bling_mlt_stats st;
-      if (bling_mlt_pass(ctx, 0x0B11A6u, (uint32_t)p, splat.data(), &st) != 0) { std::fprintf(stderr, "%s\n", bling_last_error()); return 1; }
+      const int rc = device_film ? bling_mlt_pass_device(ctx, 0x0B11A6u, (uint32_t)p, splat_flags, df.splat, &st)
+                                 : bling_mlt_pass(ctx, 0x0B11A6u, (uint32_t)p, splat.data(), &st);
+      if (rc != 0) { std::fprintf(stderr, "%s\n", bling_last_error()); return 1; }
       const float t = 1.f / (float)p;
       b = (1.f - t) * b + t * (float)st.b;
       std::printf("pass %d: %.1f ms, %llu mutations (%llu large, %llu accepted), b = %g, %.2f Mmutations/s\n", p, st.ms_total,
@@ -120,7 +185,8 @@ int main(int argc, char** argv) {
       char name[512];
       std::snprintf(name, sizeof name, "%s-%05d", out, p);
       std::printf("Writing %s...\n", name);
-      if (write_pass(ctx, dev_develop, name, film.data(), splat.data(), sw, w, h, rgb) != 0) return 1;
+      if ((device_film ? write_pass_device_film(ctx, dev_develop, df, name, film.data(), sw, w, h, rgb)
+                       : write_pass(ctx, dev_develop, name, film.data(), splat.data(), sw, w, h, rgb)) != 0) return 1;
     }
     bling_destroy(ctx);
     bling_host_free(hs);

@@ -25,6 +25,10 @@ DEFAULT_SEED = 0x0B11A6   # master seed of the benchmark
 LIGHT_RECORD = np.dtype([("photon", "<u4"), ("depth", "<u4"), ("sx", "<i4"), ("sy", "<i4"),
                          ("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("pad", "<u4")])
 
+# numpy view of bling_splat_rec (include/bling.h)
+SPLAT_REC = np.dtype([("pixel", "<u4"), ("pad", "<u4"), ("key", "<u8"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
+                      ("pad2", "<u4")])
+
 # numpy view of bling_mlt_record (include/bling.h)
 MLT_RECORD = np.dtype([("chain", "<u4"), ("mutation", "<u4"), ("x", "<f4"), ("y", "<f4"), ("i_prop", "<f4"),
                        ("a", "<f4"), ("flags", "<u4"), ("pad", "<u4")])
@@ -464,6 +468,51 @@ class Context:
                                            _ffi.u32ptr(starts), _ffi.f32ptr(b)))
         return rec[:n.value], starts, np.float32(b[0])
 
+    def _splat_tensor(self, splat):
+        """Device pointer of a splat image tensor (float32, w * h * 3, contiguous, on a device), checked as
+        develop checks its buffers; BlingError(-4) without a scene, as the size is the scene's."""
+        if self.job is None:
+            raise BlingError(-4, "no scene uploaded")
+        return self._develop_tensor(splat, "splat", "float32", self.job.width * self.job.height * 3)
+
+    def light_pass_device(self, splat, seed=DEFAULT_SEED, pass_index=1, ordered=False, flags=None):
+        """bling_light_pass_device: one light tracer pass accumulated into a device splat image (a float32
+        tensor of w * h * 3 elements on this context's first device), which never visits the host.
+        ordered=True adds every pixel's splats one at a time in (photon, depth) order (BLING_SPLAT_ORDERED):
+        the same bits on every run, equal to the CPU restatement's image.  Returns LightStats."""
+        ptr = self._splat_tensor(splat)
+        st = _ffi.LightStats()
+        fl = (_ffi.SPLAT_ORDERED if ordered else 0) if flags is None else int(flags)
+        _check(_ffi.hip().bling_light_pass_device(self._h, seed, pass_index, fl, C.c_void_p(ptr), C.byref(st)))
+        return st
+
+    def mlt_pass_device(self, splat, seed=DEFAULT_SEED, pass_index=1, ordered=False, flags=None):
+        """bling_mlt_pass_device: one Metropolis pass accumulated into a device splat image, as
+        light_pass_device; ordered=True adds in (chain, mutation, current before proposal) order.
+        Returns MltStats."""
+        ptr = self._splat_tensor(splat)
+        st = _ffi.MltStats()
+        fl = (_ffi.SPLAT_ORDERED if ordered else 0) if flags is None else int(flags)
+        _check(_ffi.hip().bling_mlt_pass_device(self._h, seed, pass_index, fl, C.c_void_p(ptr), C.byref(st)))
+        return st
+
+    def splat_merge(self, records, splat):
+        """bling_debug_splat_merge: the ordered merge alone, of a SPLAT_REC array into a device splat image."""
+        rec = np.ascontiguousarray(records, SPLAT_REC)
+        ptr = self._splat_tensor(splat)
+        _check(_ffi.hip().bling_debug_splat_merge(self._h, C.c_void_p(rec.ctypes.data) if len(rec) else None, len(rec),
+                                                  C.c_void_p(ptr)))
+
+    def set_splat_budget(self, max_records=0):
+        """bling_debug_set_splat_budget: the record budget of this context's ordered passes (0: the default)."""
+        _check(_ffi.hip().bling_debug_set_splat_budget(self._h, int(max_records)))
+
+    def splat_times(self):
+        """bling_debug_splat_times: (ms in the photon / chain launches, ms in the merges) of the last ordered pass."""
+        a, b = C.c_double(), C.c_double()
+        _check(_ffi.hip().bling_debug_splat_times(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def mlt_set_boot(self, values=None):
         """bling_debug_mlt_set_boot: bootstrap contributions that replace the evaluated ones (None: off)."""
         v = np.zeros(0, np.float32) if values is None else np.ascontiguousarray(values, np.float32)
@@ -540,63 +589,85 @@ class SPPMRenderer:
         return film, splat
 
 
+def _device_splat(job: Job, device: int):
+    """A zeroed splat image (w * h * 3 float32) on the device, as a torch tensor."""
+    import torch
+    return torch.zeros(job.width * job.height * 3, dtype=torch.float32, device=f"cuda:{device}")
+
+
 class LightTracerRenderer:
     """``instance Renderer LightTracer`` (Renderer/LightTracer.hs:37-52) on the MI355X core: passes
     1, 2, ... until the reporter returns False; each PassDone carries the (empty) film, the
-    accumulated splat image and the splat weight 1 / (pass * passPhotons) of `PassDone n img'` (:50)."""
+    accumulated splat image and the splat weight 1 / (pass * passPhotons) of `PassDone n img'` (:50).
+    device_film keeps the splat image in a device tensor for the whole run (PassDone then carries that
+    tensor, and render returns it); ordered adds the splats in the reference's order (BLING_SPLAT_ORDERED)
+    and implies a device image during the passes -- without device_film it comes back as a numpy array."""
 
-    def __init__(self, device: int = 0, seed: int = DEFAULT_SEED):
+    def __init__(self, device: int = 0, seed: int = DEFAULT_SEED, ordered: bool = False, device_film: bool = False):
         self.device = device
         self.seed = seed
+        self.ordered = ordered
+        self.device_film = device_film
 
     def render(self, job: Job, report):
         ppp = job.light.pass_photons
         ctx = Context(self.device)
         ctx.upload(job)
         film = np.zeros(job.width * job.height * 4, np.float32)
-        splat = np.zeros(job.width * job.height * 3, np.float32)
+        on_device = self.ordered or self.device_film
+        splat = _device_splat(job, self.device) if on_device else np.zeros(job.width * job.height * 3, np.float32)
         report(Progress("Started"))
         p = 1
         while True:
-            splat, st = ctx.light_pass(seed=self.seed, pass_index=p, splat=splat)
+            if on_device:
+                st = ctx.light_pass_device(splat, seed=self.seed, pass_index=p, ordered=self.ordered)
+            else:
+                splat, st = ctx.light_pass(seed=self.seed, pass_index=p, splat=splat)
             info = st.as_dict()
-            info["splat"] = splat
+            info["splat"] = splat if self.device_film or not on_device else splat.cpu().numpy()
             info["splat_weight"] = 1.0 / (p * ppp)
             if not report(Progress("PassDone", p, film, info)):
                 break
             p += 1
         ctx.close()
-        return film, splat
+        return film, splat if self.device_film or not on_device else splat.cpu().numpy()
 
 
 class MetropolisRenderer:
     """``instance Renderer Metropolis`` (Renderer/Metropolis.hs:59-120) on the MI355X core: passes 1, 2,
     ... until the reporter returns False; each PassDone carries the (empty) film, the accumulated splat
-    image and the splat weight bnext / p of `PassDone p img' (bnext / p)` (:115-117)."""
+    image and the splat weight bnext / p of `PassDone p img' (bnext / p)` (:115-117).  ordered and
+    device_film as LightTracerRenderer's."""
 
-    def __init__(self, device: int = 0, seed: int = DEFAULT_SEED):
+    def __init__(self, device: int = 0, seed: int = DEFAULT_SEED, ordered: bool = False, device_film: bool = False):
         self.device = device
         self.seed = seed
+        self.ordered = ordered
+        self.device_film = device_film
 
     def render(self, job: Job, report):
         from .film import mlt_bnext
         ctx = Context(self.device)
         ctx.upload(job)
         film = np.zeros(job.width * job.height * 4, np.float32)
-        splat = np.zeros(job.width * job.height * 3, np.float32)
+        on_device = self.ordered or self.device_film
+        splat = _device_splat(job, self.device) if on_device else np.zeros(job.width * job.height * 3, np.float32)
         report(Progress("Started"))
         p, b = 1, np.float32(1)
         while True:
-            splat, st = ctx.mlt_pass(seed=self.seed, pass_index=p, splat=splat)
+            if on_device:
+                st = ctx.mlt_pass_device(splat, seed=self.seed, pass_index=p, ordered=self.ordered)
+            else:
+                splat, st = ctx.mlt_pass(seed=self.seed, pass_index=p, splat=splat)
             b = mlt_bnext(p, b, st.b)
             info = st.as_dict()
-            info["splat"] = splat
+            info["splat"] = splat if self.device_film or not on_device else splat.cpu().numpy()
             info["splat_weight"] = float(np.float32(b / np.float32(p)))
             if not report(Progress("PassDone", p, film, info)):
                 break
             p += 1
         ctx.close()
-        return film, splat
+        return film, splat if self.device_film or not on_device else splat.cpu().numpy()
 
 
 RENDERER_LIGHT = 3   # BLING_RENDERER_LIGHT (include/bling_scene.h)

@@ -431,6 +431,53 @@ int bling_debug_mlt_boot(const float* I, uint32_t n, uint32_t seed, uint32_t pas
  * evaluated); n = 0 or a scene upload ends it. */
 int bling_debug_mlt_set_boot(bling_ctx* ctx, const float* I, uint32_t n);
 
+/* ---- splat images on the device, and ordered splat films ----
+ * bling_light_pass_device / bling_mlt_pass_device are bling_light_pass / bling_mlt_pass with the splat
+ * image in a caller-owned device buffer: splat_device holds W*H*3 floats (XYZ) on device_ids[0] (e.g. a
+ * torch tensor's data_ptr()), is ACCUMULATED into and never copied to the host; it must not be NULL and
+ * feeds bling_film_develop_device directly as splat_dev.  The calls run on the context's stream and return
+ * after completion; the context's own splat image is not touched.
+ *   flags == 0: the splats are added with float atomics, as in the host-buffer calls: the same arithmetic,
+ *     counters and records, and an image that differs from theirs only in the order of its binary32 sums.
+ *   BLING_SPLAT_ORDERED: every pixel's new value is its old value plus that pixel's splats of this pass,
+ *     added one at a time in binary32 in the reference's order -- the light tracer's by (photon, depth)
+ *     (replicateM_ ppp oneRay into one image, LightTracer.hs:41-50), Metropolis' by (chain, mutation, the
+ *     current sample before the proposal) (Metropolis.hs:96-104).  No float atomic is used.  The image is
+ *     the same on every run, whatever the launch geometry, chunking or timing, and equals the CPU
+ *     restatements' binary32 images bit for bit; the stats equal the atomic mode's.
+ *     The splats go through a record buffer of at most `budget` records (default: a sixteenth of the
+ *     device's memory at 56 bytes a record, between 2^16 and 2^27 records).  The light tracer merges
+ *     ascending photon ranges one after another and halves a range whose records exceed the budget; a single
+ *     photon that alone exceeds it is BLING_EINVAL (the image then holds the ranges before it).  Metropolis
+ *     merges once a pass: 2 M records (M = mutations) beyond the budget are refused with BLING_EINVAL
+ *     before any launch, the image untouched.
+ * Errors: those of bling_light_pass / bling_mlt_pass, and BLING_EINVAL for unknown flag bits or a NULL
+ * splat_device.  SPPM's splat image is not served. */
+#define BLING_SPLAT_ORDERED 1u
+int bling_light_pass_device(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, uint32_t flags, void* splat_device,
+                            bling_light_stats* stats);
+int bling_mlt_pass_device(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, uint32_t flags, void* splat_device,
+                          bling_mlt_stats* stats);
+
+/* Test hook: the ordered merge alone.  n host records in any order are merged into splat_device (W*H*3
+ * floats on device_ids[0]): for every pixel with records, img = (((img + r0) + r1) + ...) per channel in
+ * binary32, its records in ascending key order; other pixels stay as they are.  Records with equal keys
+ * merge in any order among themselves.  Needs an uploaded scene for W and H only; BLING_EINVAL for a pixel
+ * index beyond W*H. */
+typedef struct bling_splat_rec {
+    uint32_t pixel;            /* y * W + x                                                       */
+    uint32_t pad;
+    uint64_t key;              /* the order within the pixel                                      */
+    float    x, y, z;          /* the XYZ the splat adds                                          */
+    uint32_t pad2;
+} bling_splat_rec;
+int bling_debug_splat_merge(bling_ctx* ctx, const bling_splat_rec* recs, size_t n, void* splat_device);
+/* Test hook: the record budget of this context's ordered passes; 0 restores the default. */
+int bling_debug_set_splat_budget(bling_ctx* ctx, size_t max_records);
+/* Diagnostics: device time of the context's last ordered pass, split into its photon / chain launches and
+ * its merges (their sum is the pass's ms_total). */
+int bling_debug_splat_times(bling_ctx* ctx, double* ms_kernel, double* ms_merge);
+
 /* Diagnostics (no reference counterpart): the path-state bytes the shading kernel k_shade moved in
  * the context's last bling_render_pass*, per stream and direction -- out[2 k] read, out[2 k + 1]
  * written, stream k in the order BLING_STREAM_NAMES lists -- counted where the algorithm needs
