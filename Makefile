@@ -10,6 +10,7 @@
 #   tests/ref/_build/libbd_ref.so     CPU restatement of the bidirectional integrator over the oracle (tests)
 #   tests/ref/_build/libmlt_ref.so    CPU restatement of the Metropolis renderer over that one (tests)
 #   tests/ref/_build/libnm_ref.so     CPU restatement of the normal-map integrator over the oracle (tests)
+#   tests/ref/_build/libsppm_ref.so   per-splat records of SPPM's photon pass over the oracle (tests)
 
 HIPCC    ?= /opt/rocm/bin/hipcc
 ROCM     ?= $(patsubst %/bin/,%,$(dir $(HIPCC)))
@@ -51,7 +52,7 @@ HIPFLAGS  := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -ffp-contract=off -fno-
 
 all: $(LIBDIR)/libbling_host.so $(LIBDIR)/libbling_hip.so $(ORADIR)/liboracle.so $(LIBDIR)/bling \
      $(LIBDIR)/libbling_mathcheck.so $(LTRDIR)/liblt_ref.so $(LTRDIR)/libbd_ref.so \
-     $(LTRDIR)/libmlt_ref.so $(LTRDIR)/libnm_ref.so
+     $(LTRDIR)/libmlt_ref.so $(LTRDIR)/libnm_ref.so $(LTRDIR)/libsppm_ref.so
 
 host: $(LIBDIR)/libbling_host.so
 oracle: $(ORADIR)/liboracle.so
@@ -60,6 +61,7 @@ ltref: $(LTRDIR)/liblt_ref.so
 bdref: $(LTRDIR)/libbd_ref.so
 mltref: $(LTRDIR)/libmlt_ref.so
 nmref: $(LTRDIR)/libnm_ref.so
+sppmref: $(LTRDIR)/libsppm_ref.so
 
 $(LIBDIR)/libbling_host.so: $(HOST_SRC) $(HOST_HDR)
 	@mkdir -p $(LIBDIR)
@@ -88,6 +90,11 @@ $(LTRDIR)/libmlt_ref.so: tests/ref/mlt_ref.cpp tests/ref/bidir_ref.cpp $(REF_HDR
 $(LTRDIR)/libnm_ref.so: tests/ref/normals_ref.cpp $(ORA_SRC) $(ORA_HDR)
 	@mkdir -p $(LTRDIR)
 	$(CXX) $(HOSTFLAGS) -Wno-subobject-linkage -fopenmp -shared -o $@ tests/ref/normals_ref.cpp
+
+# SPPM's photon records, built like the light tracer's; tests only
+$(LTRDIR)/libsppm_ref.so: tests/ref/sppm_ref.cpp $(ORA_SRC) $(ORA_HDR)
+	@mkdir -p $(LTRDIR)
+	$(CXX) $(HOSTFLAGS) -Wno-subobject-linkage -fopenmp -shared -o $@ tests/ref/sppm_ref.cpp
 
 # one object per unit (core, sppm driver, one per kernel feature profile) so make -j compiles the
 # kernel instantiations in parallel
@@ -125,4 +132,4 @@ variant: $(CORE_OBJ)
 clean:
 	rm -rf $(LIBDIR) $(ORADIR) $(LTRDIR) build
 
-.PHONY: all host oracle core ltref bdref mltref nmref clean variant
+.PHONY: all host oracle core ltref bdref mltref nmref sppmref clean variant

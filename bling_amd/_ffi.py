@@ -73,6 +73,13 @@ class LightStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SppmRecord(C.Structure):
+    """bling_sppm_record (include/bling.h)."""
+    _fields_ = [("thread", C.c_uint32), ("photon", C.c_uint32), ("seq", C.c_uint32), ("depth", C.c_uint32),
+                ("sx", C.c_int32), ("sy", C.c_int32), ("x", C.c_float), ("y", C.c_float), ("z", C.c_float),
+                ("pad", C.c_uint32)]
+
+
 class LightRecord(C.Structure):
     """bling_light_record (include/bling.h): one splat of the light tracer's record mode, 32 bytes."""
     _fields_ = [("photon", C.c_uint32), ("depth", C.c_uint32), ("sx", C.c_int32), ("sy", C.c_int32),
@@ -136,6 +143,9 @@ def host() -> C.CDLL:
         lib.bling_host_load.restype = C.c_int
         lib.bling_host_desc.argtypes = [C.c_void_p]
         lib.bling_host_desc.restype = C.c_void_p
+        if hasattr(lib, "bling_host_sppm_splat_weight"):
+            lib.bling_host_sppm_splat_weight.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+            lib.bling_host_sppm_splat_weight.restype = C.c_float
         lib.bling_host_summary.argtypes = [C.c_void_p]
         lib.bling_host_summary.restype = C.c_char_p
         lib.bling_host_free.argtypes = [C.c_void_p]
@@ -171,7 +181,7 @@ HIP_SYMBOLS = ["bling_create", "bling_scene_upload", "bling_scene_validate", "bl
                "bling_trace", "bling_trace_device", "bling_sample_li", "bling_sample_li_vertices", "bling_pass_tile_layout",
                "bling_film_add_tiles", "bling_film_add_shards", "bling_sppm_pass", "bling_sppm_pixel_stats", "bling_sppm_reset",
                "bling_render", "bling_debug_stream_bytes", "bling_debug_scene_info", "bling_debug_mis_culled", "bling_debug_set_mis_cull", "bling_debug_set_pipeline", "bling_debug_pass_results", "bling_debug_compact", "bling_debug_sppm_hitpoints", "bling_debug_sppm_buckets",
-               "bling_film_develop", "bling_film_develop_device", "bling_light_pass", "bling_debug_light_records", "bling_mlt_pass", "bling_debug_mlt_records", "bling_debug_mlt_boot", "bling_debug_mlt_set_boot", "bling_light_pass_device", "bling_mlt_pass_device", "bling_debug_splat_merge", "bling_debug_set_splat_budget", "bling_debug_splat_times", "bling_debug_bidir_terms", "bling_destroy", "bling_last_error", "bling_version"]
+               "bling_film_develop", "bling_film_develop_device", "bling_light_pass", "bling_debug_light_records", "bling_mlt_pass", "bling_debug_mlt_records", "bling_debug_mlt_boot", "bling_debug_mlt_set_boot", "bling_light_pass_device", "bling_mlt_pass_device", "bling_debug_splat_merge", "bling_debug_set_splat_budget", "bling_debug_splat_times", "bling_sppm_pass_device", "bling_debug_sppm_records", "bling_debug_bidir_terms", "bling_destroy", "bling_last_error", "bling_version"]
 
 
 class Progress(C.Structure):
@@ -263,6 +273,13 @@ def hip() -> C.CDLL:
             lib.bling_debug_set_splat_budget.restype = C.c_int
             lib.bling_debug_splat_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
             lib.bling_debug_splat_times.restype = C.c_int
+        if hasattr(lib, "bling_sppm_pass_device"):    # older experiment builds lack SPPM's device images
+            lib.bling_sppm_pass_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                   C.POINTER(SppmStats)]
+            lib.bling_sppm_pass_device.restype = C.c_int
+            lib.bling_debug_sppm_records.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                     C.POINTER(SppmRecord), C.c_size_t, C.POINTER(C.c_size_t)]
+            lib.bling_debug_sppm_records.restype = C.c_int
         if hasattr(lib, "bling_debug_bidir_terms"):   # older experiment builds lack it
             lib.bling_debug_bidir_terms.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.c_size_t,
                                                     c_f32p, C.POINTER(C.c_int32)]

@@ -1422,16 +1422,26 @@ int bling_trace_device(bling_ctx* c, const void* rays, size_t n, int any_hit, vo
   });
 }
 
+static int sppm_ready(bling_ctx* c) {
+  if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
+  if (c->cfg.renderer != BLING_RENDERER_SPPM) throw std::invalid_argument("the uploaded scene's renderer is not sppm");
+  if (c->features & FT_PROCTEX) {
+    g_err = "sppm: blend / gradient / checker / cellNoise textures are not supported by the SPPM renderer";
+    return BLING_EUNSUPPORTED;
+  }
+  return BLING_OK;
+}
+
+static void sppm_launch(bling_ctx* c, uint32_t seed, uint32_t pass, float* film, float* splat, uint32_t flags, bling_sppm_stats* st) {
+  if ((c->features & ~kProfiles[0]) == 0u) sppm_pass_t<kProfiles[0]>(c, seed, pass, film, splat, flags, st);
+  else sppm_pass_t<kSppmAll>(c, seed, pass, film, splat, flags, st);
+}
+
 int bling_sppm_pass(bling_ctx* c, uint32_t seed, uint32_t pass_index, float* film_out, float* splat_out,
                     bling_sppm_stats* st) {
   return guarded([&] {
     if (!c) throw std::invalid_argument("null argument");
-    if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
-    if (c->cfg.renderer != BLING_RENDERER_SPPM) throw std::invalid_argument("the uploaded scene's renderer is not sppm");
-    if (c->features & FT_PROCTEX) {
-      g_err = "sppm: blend / gradient / checker / cellNoise textures are not supported by the SPPM renderer";
-      return BLING_EUNSUPPORTED;
-    }
+    if (int rc = sppm_ready(c)) return rc;
     HIPCHK(hipSetDevice(c->device));
     if (!c->sppm.ready) sppm_init(c);
     SppmState& P = c->sppm;
@@ -1441,11 +1451,67 @@ int bling_sppm_pass(bling_ctx* c, uint32_t seed, uint32_t pass_index, float* fil
     if (splat_out) HIPCHK(hipMemcpy(P.splat.p, splat_out, ns * sizeof(float), hipMemcpyHostToDevice));
     else HIPCHK(hipMemset(P.splat.p, 0, ns * sizeof(float)));
     if (st) std::memset(st, 0, sizeof *st);
-    if ((c->features & ~kProfiles[0]) == 0u) sppm_pass_t<kProfiles[0]>(c, seed, pass_index, st);
-    else sppm_pass_t<kSppmAll>(c, seed, pass_index, st);
+    sppm_launch(c, seed, pass_index, P.film.p, P.splat.p, 0u, st);
     if (film_out) HIPCHK(hipMemcpy(film_out, P.film.p, nf * sizeof(float), hipMemcpyDeviceToHost));
     if (splat_out) HIPCHK(hipMemcpy(splat_out, P.splat.p, ns * sizeof(float), hipMemcpyDeviceToHost));
-    return BLING_OK;
+    return (int)BLING_OK;
+  });
+}
+
+int bling_sppm_pass_device(bling_ctx* c, uint32_t seed, uint32_t pass_index, uint32_t flags, void* film_device, void* splat_device,
+                           bling_sppm_stats* st) {
+  return guarded([&] {
+    if (!c) throw std::invalid_argument("null argument");
+    if (flags & ~BLING_SPLAT_ORDERED) throw std::invalid_argument("unknown splat flag bits " + std::to_string(flags & ~BLING_SPLAT_ORDERED));
+    if (int rc = sppm_ready(c)) return rc;
+    if (!c->peers.empty()) throw std::invalid_argument("bling_sppm_pass_device runs on a single-device context");
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->sppm.ready) sppm_init(c);
+    if (st) std::memset(st, 0, sizeof *st);
+    sppm_launch(c, seed, pass_index, static_cast<float*>(film_device), static_cast<float*>(splat_device), flags, st);
+    return (int)BLING_OK;
+  });
+}
+
+int bling_debug_sppm_records(bling_ctx* c, uint32_t seed, uint32_t pass_index, uint32_t thread, uint32_t first_photon,
+                             uint32_t n_photons, bling_sppm_record* records, size_t cap, size_t* n) {
+  return guarded([&] {
+    if (!c || !n || (cap && !records)) throw std::invalid_argument("null argument");
+    *n = 0;
+    if (int rc = sppm_ready(c)) return rc;
+    if (!c->peers.empty()) throw std::invalid_argument("bling_debug_sppm_records runs on a single-device context");
+    const uint32_t sn = sppm_sn(c);
+    if (thread >= (uint32_t)std::max(1, c->cfg.sppm_threads)) throw std::invalid_argument("sampler beyond sppm_threads");
+    if ((uint64_t)first_photon + n_photons > (uint64_t)sn * sn) throw std::invalid_argument("photon range beyond the sampler's sn^2");
+    if (cap > 0x7FFFFFFFull) throw std::invalid_argument("record capacity too large");
+    if (n_photons == 0) return (int)BLING_OK;
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->sppm.ready) sppm_init(c);
+    // a launch needs a buffer to claim slots in: one record at least, so the count is always known
+    const uint32_t rcap = (uint32_t)std::max<size_t>(cap, 1);
+    const uint32_t got = (c->features & ~kProfiles[0]) == 0u
+                             ? sppm_records_t<kProfiles[0]>(c, seed, pass_index, thread, first_photon, n_photons, rcap)
+                             : sppm_records_t<kSppmAll>(c, seed, pass_index, thread, first_photon, n_photons, rcap);
+    *n = got;
+    if (got > cap) {
+      g_err = "sppm records: " + std::to_string(got) + " records exceed the capacity " + std::to_string(cap);
+      return (int)BLING_EINVAL;
+    }
+    std::vector<uint4> raw((size_t)2 * got);
+    if (got) HIPCHK(hipMemcpy(raw.data(), c->sppm.rec.p, raw.size() * sizeof(uint4), hipMemcpyDeviceToHost));
+    const uint32_t W = (uint32_t)c->S.width;
+    for (uint32_t i = 0; i < got; ++i) {
+      const uint4 a = raw[2 * (size_t)i], b = raw[2 * (size_t)i + 1];
+      bling_sppm_record& r = records[i];
+      r.thread = thread; r.photon = a.w; r.seq = a.z; r.depth = a.y;
+      r.sx = (int32_t)(a.x % W); r.sy = (int32_t)(a.x / W);
+      std::memcpy(&r.x, &b.x, 3 * sizeof(float));
+      r.pad = 0u;
+    }
+    std::sort(records, records + got, [](const bling_sppm_record& p, const bling_sppm_record& q) {
+      return p.photon != q.photon ? p.photon < q.photon : p.seq < q.seq;
+    });
+    return (int)BLING_OK;
   });
 }
 

@@ -105,7 +105,15 @@ struct SppmState {
   DBuf<SppmGrid> grid;
   DBuf<unsigned long long> ctr;
   DBuf<TileDesc> tiles;
+  // ordered mode (BLING_SPLAT_ORDERED): the tile images of the eye film, one sampler's splat image, one
+  // launch's counts, counters, records and record count
+  DBuf<float4> timg;
+  DBuf<float> thread_img;
+  DBuf<uint32_t> cnt_tmp, rec_count;
+  DBuf<unsigned long long> rctr;
+  DBuf<uint4> rec;
   void free_all() {
+    timg.free(); thread_img.free(); cnt_tmp.free(); rec_count.free(); rctr.free(); rec.free();
     for (auto* b : {&hp_pos, &hp_hit, &hp_o, &hp_d, &hp_f, &result}) b->free();
     img.free(); hp_bsdf.free();
     for (auto* b : {&hp_count, &cnt, &bstart, &bcur, &items}) b->free();
@@ -574,7 +582,14 @@ int run_wave_pair_prof(bling_ctx* c, const HalfWave* h, uint32_t seed, uint32_t 
 template <uint32_t F>
 void launch_trace_prof(bling_ctx* c, const float* rays, uint32_t n, int any_hit, float* t, uint32_t* prim, float* bary);
 template <uint32_t F>
-void sppm_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, bling_sppm_stats* st);
+void sppm_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, float* film, float* splat, uint32_t flags, bling_sppm_stats* st);
+// The splat records of photons first .. first + count - 1 of sampler k (sppm_pass.hip), after an eye pass and
+// hash of its own for the context's current radii; neither image nor the pixel statistics are touched.
+// Returns the records claimed (which may exceed rec_cap); the first min(claimed, rec_cap) are in c->sppm.rec.
+template <uint32_t F>
+uint32_t sppm_records_t(bling_ctx* c, uint32_t seed, uint32_t pass, uint32_t k, uint32_t first, uint32_t count, uint32_t rec_cap);
+// sn of the photon samplers (SPPM.hs:441-453, 474); throws where a pass would hold too many photons
+uint32_t sppm_sn(const bling_ctx* c);
 void sppm_init(bling_ctx* c);
 // One light tracer launch (light_pass.hip): photons first .. first + count - 1 of the pass into the
 // device image splat (nullptr = none) and / or the context's record buffer of rec_cap records (0 = off);

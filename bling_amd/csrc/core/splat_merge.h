@@ -27,8 +27,10 @@ constexpr uint32_t SM_LDS_RECORDS = 4096;    // longest segment sorted in LDS (4
 //                    pixel = sy * W + sx, key = photon << 32 | depth
 enum : int { SM_LAYOUT_SPLAT = 0, SM_LAYOUT_LIGHT = 1 };
 
-DEV void sm_write_rec(uint4* __restrict__ rec, size_t slot, uint32_t pixel, unsigned long long key, float x, float y, float z) {
-  rec[2 * slot] = make_uint4(pixel, 0u, (uint32_t)key, (uint32_t)(key >> 32));
+// tag: the record's spare word, which the merge does not read
+DEV void sm_write_rec(uint4* __restrict__ rec, size_t slot, uint32_t pixel, unsigned long long key, float x, float y, float z,
+                      uint32_t tag = 0u) {
+  rec[2 * slot] = make_uint4(pixel, tag, (uint32_t)key, (uint32_t)(key >> 32));
   rec[2 * slot + 1] = make_uint4(__float_as_uint(x), __float_as_uint(y), __float_as_uint(z), 0u);
 }
 

@@ -15,6 +15,7 @@
 // from the reference's per-thread images, the set of contributions does not.
 #pragma once
 #include "wavefront.h"
+#include "splat_merge.h"
 
 namespace bd {
 
@@ -486,21 +487,33 @@ DEV float light_ray(const DevScene& S, const bling_light& L, float uo1, float uo
   return sint == 0.f ? 0.f : pdDir * pdArea;
 }
 
-template <uint32_t F>
+// Record mode (REC, BLING_SPLAT_ORDERED): the launch covers photons first .. first + count - 1 of sampler k
+// alone.  A splat becomes one record (splat_merge.h, SM_LAYOUT_SPLAT: key photon << 32 | seq, seq the running
+// index of the photon's (vertex, hit point) pairs, the vertex depth in the record's spare word) in a slot an
+// integer counter hands out; B.cnt is then the launch's own n_stats counts and B.ctr its own counters, so the
+// host can discard a launch whose records did not fit.
+struct SppmRec {
+  uint4* rec;              // 2 uint4 per record; nullptr: no image is wanted, only the counts
+  uint32_t* rec_count;     // slots claimed (may exceed rec_cap: the host runs the range again)
+  uint32_t rec_cap;
+  uint32_t k, first, count;
+};
+
+template <uint32_t F, bool REC = false>
 static __global__ __launch_bounds__(256) void k_sppm_photon(const DevScene* __restrict__ Sptr, SppmBufs B, uint32_t nth,
-                                                     uint32_t sn, uint32_t seed, uint32_t pass) {
+                                                     uint32_t sn, uint32_t seed, uint32_t pass, SppmRec R) {
   extern __shared__ float4 smem[];
   const DevScene& S = *Sptr;
   const LdsScene L = lds_setup(S, smem);
   const uint32_t spp = sn * sn;
   const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
   unsigned long long rays = 0, pairs = 0, dropped = 0;
-  if (gid < nth * spp) {
-    const uint32_t k = gid / spp;
-    const uint32_t ppk = brng::pixel_key(seed, pass, SPPM_PHOTON_PIXEL | k), pn = gid - k * spp;
+  if (gid < (REC ? R.count : nth * spp)) {
+    const uint32_t k = REC ? R.k : gid / spp;
+    const uint32_t ppk = brng::pixel_key(seed, pass, SPPM_PHOTON_PIXEL | k), pn = REC ? R.first + gid : gid - k * spp;
     PhotonSampler ps{ppk, pn, spp, sn, 1.f / (float)spp, 1.f / (float)sn, brng::sample_key(ppk, pn)};
     const SppmGrid g = *B.grid;
-    uint32_t* cnt = B.cnt + (size_t)k * B.n_stats;
+    uint32_t* cnt = REC ? B.cnt : B.cnt + (size_t)k * B.n_stats;
     const float ul = ps.rnd1(0);
     float uo1, uo2, ud1, ud2;
     ps.rnd2(0, &uo1, &uo2);
@@ -536,6 +549,7 @@ static __global__ __launch_bounds__(256) void k_sppm_photon(const DevScene* __re
         const uint32_t b = sppm_bucket((int64_t)fabsf(q.x * g.scale), (int64_t)fabsf(q.y * g.scale),
                                        (int64_t)fabsf(q.z * g.scale), g.cnt);
         kd_lookup(B, B.bstart[b], B.bstart[b + 1], p, [&](uint32_t i, const float4& hp) {
+          const uint32_t seq = (uint32_t)pairs;
           ++pairs;
           const float4 ho = B.hp_o[i], hd = B.hp_d[i];
           const Bsdf hb = B.hp_bsdf[i];
@@ -547,8 +561,17 @@ static __global__ __launch_bounds__(256) void k_sppm_photon(const DevScene* __re
             else {
               float x, y, z;
               to_xyz(l, &x, &y, &z);
-              float* o = B.splat + 3 * ((size_t)sy * S.width + sx);
-              atomicAdd(&o[0], x); atomicAdd(&o[1], y); atomicAdd(&o[2], z);
+              if (REC) {
+                if (R.rec) {
+                  const uint32_t slot = atomicAdd(R.rec_count, 1u);
+                  if (slot < R.rec_cap)
+                    sm_write_rec(R.rec, slot, (uint32_t)sy * (uint32_t)S.width + (uint32_t)sx,
+                                 (unsigned long long)pn << 32 | seq, x, y, z, (uint32_t)d);
+                }
+              } else {
+                float* o = B.splat + 3 * ((size_t)sy * S.width + sx);
+                atomicAdd(&o[0], x); atomicAdd(&o[1], y); atomicAdd(&o[2], z);
+              }
             }
           }
           atomicAdd(&cnt[sppm_sidx(S, ho.w, hd.w)], 1u);
@@ -593,6 +616,110 @@ static __global__ __launch_bounds__(256) void k_sppm_stats(SppmBufs B, uint32_t 
     B.r2[i] = r2 * ratio;
     B.nacc[i] = n2;
   }
+}
+
+// ------------------------------------------------------------------ ordered mode (BLING_SPLAT_ORDERED)
+// A bucket of at most five entries is a Leaf that mkKdTree never sorts: treeLookup meets its hit points in
+// the order mkHash inserted them, the order of the hit point list -- tile by tile, a tile's pixels by
+// (iy, ix), a pixel's eye tree in preorder, reflection first (traceCam).  k_sppm_cells fills a bucket in
+// the order of its atomics, so the ordered pass puts such buckets into the reference's order: the rank
+// below, from the hit point's key alone.  Larger buckets are ordered by k_sppm_kd's sorts already.
+DEV unsigned long long sppm_list_rank(const DevScene& S, unsigned long long key) {
+  const uint32_t pixel = (uint32_t)(key >> 24), id = (uint32_t)key & 0xFFFFFFu;
+  const uint32_t ex = pixel % (uint32_t)S.ext_w, ey = pixel / (uint32_t)S.ext_w;
+  const uint32_t bits = 32u - (uint32_t)__clz((int)id);                // id >= 1: depth + 1
+  const uint32_t pre = (id << (24u - bits)) << 5 | bits;               // an ancestor before its subtree, 2 id before 2 id + 1
+  return (unsigned long long)(ey >> 4) << 49 | (unsigned long long)(ex >> 4) << 37 | (unsigned long long)(ey & 15u) << 33 |
+         (unsigned long long)(ex & 15u) << 29 | pre;
+}
+static __global__ __launch_bounds__(256) void k_sppm_leaf_order(const DevScene* __restrict__ Sptr, SppmBufs B) {
+  const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B.grid->cnt) return;
+  const uint32_t b0 = B.bstart[b], n = B.bstart[b + 1] - b0;
+  if (n < 2u || n > 5u) return;
+  uint32_t v[5];
+  unsigned long long r[5];
+  for (uint32_t i = 0; i < n; ++i) { v[i] = B.items[b0 + i]; r[i] = sppm_list_rank(*Sptr, B.hp_key[v[i]]); }
+  for (uint32_t i = 1; i < n; ++i)                                      // insertion sort; equal ranks are one hit point
+    for (uint32_t j = i; j > 0 && r[j] < r[j - 1]; --j) {
+      const unsigned long long tr = r[j]; r[j] = r[j - 1]; r[j - 1] = tr;
+      const uint32_t tv = v[j]; v[j] = v[j - 1]; v[j - 1] = tv;
+    }
+  for (uint32_t i = 0; i < n; ++i) B.items[b0 + i] = v[i];
+}
+
+// The eye film without atomics.  One block per extent tile; a thread owns pixels of the tile image
+// (mkImageTile: origin (ox, oy), w x h, at most FILM_TILE_MAX^2) and adds to each, in a register from zero,
+// the filtered contribution of the tile's samples in (iy, ix) order -- k_film's index arithmetic, clipping,
+// r.w == 0 skip and trap T12, with the loops turned inside out.  The tile image goes to the tile's slot of
+// FILM_TILE_MAX^2 float4 (W, X, Y, Z).
+static __global__ __launch_bounds__(256) void k_sppm_film_ordered(const DevScene* __restrict__ Sptr, WaveState W,
+                                                           const TileDesc* __restrict__ tiles, float4* __restrict__ timg) {
+  __shared__ float4 sres[256];
+  __shared__ float2 simg[256];
+  __shared__ float tbl[256];
+  const DevScene& S = *Sptr;
+  const TileDesc td = tiles[blockIdx.x];
+  const float fw = S.filter_w, fh = S.filter_h;
+  const int ox = max(0, td.x0), oy = max(0, td.y0);
+  const int w = td.x1 - ox + (int)floorf(0.5f + fw), h = td.y1 - oy + (int)floorf(0.5f + fh);
+  const uint32_t count = min(td.count, 256u);
+  if (threadIdx.x < count) { sres[threadIdx.x] = W.result[td.offset + threadIdx.x]; simg[threadIdx.x] = W.img[td.offset + threadIdx.x]; }
+  tbl[threadIdx.x] = S.filter_table[threadIdx.x];
+  __syncthreads();
+  const float ifw = 1.f / fw, ifh = 1.f / fw;                            // trap T12
+  float4* slot = timg + (size_t)blockIdx.x * FILM_TILE_MAX * FILM_TILE_MAX;
+  const int tw = min(w, FILM_TILE_MAX), th = min(h, FILM_TILE_MAX);
+  for (int q = threadIdx.x; q < tw * th; q += blockDim.x) {
+    const int x = ox + q % tw, y = oy + q / tw;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    for (uint32_t j = 0; j < count; ++j) {
+      const float4 r = sres[j];
+      if (r.w == 0.f) continue;
+      const float2 im = simg[j];
+      const float dx = im.x - 0.5f, dy = im.y - 0.5f;
+      const int x0 = max(ox, (int)ceilf(dx - fw)), x1 = min(ox + w - 1, (int)floorf(dx + fw));
+      const int y0 = max(oy, (int)ceilf(dy - fh)), y1 = min(oy + h - 1, (int)floorf(dy + fh));
+      if (x < x0 || x > x1 || y < y0 || y > y1) continue;
+      const int fy = min((int)floorf(fabsf(((float)y - dy) * ifh * 16.f)), 15);
+      const int fx = min((int)floorf(fabsf(((float)x - dx) * ifw * 16.f)), 15);
+      const float fltw = tbl[fy * 16 + fx];
+      a0 = a0 + fltw; a1 = a1 + r.x * fltw; a2 = a2 + r.y * fltw; a3 = a3 + r.z * fltw;
+    }
+    slot[(x - ox) + (y - oy) * FILM_TILE_MAX] = make_float4(a0, a1, a2, a3);
+  }
+}
+
+// addTile in tile order: one thread per film pixel adds the values of the tile images that cover it, in
+// ascending tile index, film = film + tile per channel.
+static __global__ __launch_bounds__(256) void k_sppm_film_add(const DevScene* __restrict__ Sptr, const TileDesc* __restrict__ tiles,
+                                                       uint32_t n_tiles, const float4* __restrict__ timg, float* __restrict__ film) {
+  const DevScene& S = *Sptr;
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= (uint32_t)S.width * (uint32_t)S.height) return;
+  const int gx = (int)(p % (uint32_t)S.width), gy = (int)(p / (uint32_t)S.width);
+  const int rx = (int)floorf(0.5f + S.filter_w), ry = (int)floorf(0.5f + S.filter_h);
+  float* o = film + 4 * (size_t)p;
+  float4 f = make_float4(o[0], o[1], o[2], o[3]);
+  for (uint32_t t = 0; t < n_tiles; ++t) {
+    const TileDesc td = tiles[t];
+    const int ox = max(0, td.x0), oy = max(0, td.y0);
+    const int w = min(td.x1 - ox + rx, FILM_TILE_MAX), h = min(td.y1 - oy + ry, FILM_TILE_MAX);
+    if (gx < ox || gy < oy || gx >= ox + w || gy >= oy + h) continue;
+    const float4 v = timg[(size_t)t * FILM_TILE_MAX * FILM_TILE_MAX + (gx - ox) + (gy - oy) * FILM_TILE_MAX];
+    f.x = f.x + v.x; f.y = f.y + v.y; f.z = f.z + v.z; f.w = f.w + v.w;
+  }
+  o[0] = f.x; o[1] = f.y; o[2] = f.z; o[3] = f.w;
+}
+
+// splat = splat + image_k (the samplers' images in k order), and a launch's counts into its sampler's
+static __global__ __launch_bounds__(256) void k_sppm_add_f32(float* __restrict__ dst, const float* __restrict__ src, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = dst[i] + src[i];
+}
+static __global__ __launch_bounds__(256) void k_sppm_add_u32(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] += src[i];
 }
 
 }  // namespace bd

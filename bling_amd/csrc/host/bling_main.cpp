@@ -6,11 +6,11 @@
 //         [--develop host|device] [--splat atomic|ordered]
 // --develop device makes each written pass's 8-bit and RGBE pixels on the device (bling_film_develop)
 // and hands them to the encoders; the default, host, develops with the host library.  Same files.
-// --splat ordered (light tracer and Metropolis scenes) adds every pixel's splats in the reference's order
+// --splat ordered (light tracer, Metropolis and SPPM scenes) adds every pixel's splats in the reference's order
 // (BLING_SPLAT_ORDERED): the same files on every run; the default, atomic, adds them with float atomics.
-// With --develop device, or --splat ordered, such a scene's splat image lives on the device for the whole
-// run (bling_light_pass_device / bling_mlt_pass_device); --develop device then develops it there
-// (bling_film_develop_device) and only the developed pixels come back.
+// With --develop device, or --splat ordered, such a scene's splat image (and an SPPM scene's film) lives on
+// the device for the whole run (bling_light_pass_device / bling_mlt_pass_device / bling_sppm_pass_device);
+// --develop device then develops it there (bling_film_develop_device) and only the developed pixels come back.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -139,7 +139,8 @@ int main(int argc, char** argv) {
   }
   int w = d->config.width, h = d->config.height;
   std::vector<float> film((size_t)w * h * 4, 0.f), rgb((size_t)w * h * 3);
-  const bool splats = d->config.renderer == BLING_RENDERER_LIGHT || d->config.renderer == BLING_RENDERER_METROPOLIS;
+  const bool splats = d->config.renderer == BLING_RENDERER_LIGHT || d->config.renderer == BLING_RENDERER_METROPOLIS ||
+                      d->config.renderer == BLING_RENDERER_SPPM;
   const bool device_film = splats && (dev_develop || ordered);
   const uint32_t splat_flags = ordered ? BLING_SPLAT_ORDERED : 0u;
   DeviceFilm df;
@@ -185,6 +186,34 @@ int main(int argc, char** argv) {
       char name[512];
       std::snprintf(name, sizeof name, "%s-%05d", out, p);
       std::printf("Writing %s...\n", name);
+      if ((device_film ? write_pass_device_film(ctx, dev_develop, df, name, film.data(), sw, w, h, rgb)
+                       : write_pass(ctx, dev_develop, name, film.data(), splat.data(), sw, w, h, rgb)) != 0) return 1;
+    }
+    bling_destroy(ctx);
+    bling_host_free(hs);
+    return 0;
+  }
+  if (d->config.renderer == BLING_RENDERER_SPPM) {
+    // instance Renderer SPPM (Renderer/SPPM.hs:466-480): every pass adds its eye samples to the film and its
+    // photons' splats to the splat image, and the image of pass k weighs the splats with 1 / (threads k sn^2) (:460)
+    std::vector<float> splat((size_t)w * h * 3, 0.f);
+    for (int p = 1; p <= passes; ++p) {
+      bling_sppm_stats st;
+      const int rc = device_film ? bling_sppm_pass_device(ctx, 0x0B11A6u, (uint32_t)p, splat_flags, df.film, df.splat, &st)
+                                 : bling_sppm_pass(ctx, 0x0B11A6u, (uint32_t)p, film.data(), splat.data(), &st);
+      if (rc != 0) { std::fprintf(stderr, "%s\n", bling_last_error()); return 1; }
+      std::printf("pass %d: %.1f ms, %llu hit points, %llu photons, %llu pairs\n", p, st.ms_total, (unsigned long long)st.hitpoints,
+                  (unsigned long long)st.photons, (unsigned long long)st.photon_hits);
+      const float sw = bling_host_sppm_splat_weight(&d->config, p, nullptr);
+      char name[512];
+      std::snprintf(name, sizeof name, "%s-%05d", out, p);
+      std::printf("Writing %s...\n", name);
+      // host develop of device images: the film comes back here, the splat image in write_pass_device_film
+      if (device_film && !dev_develop &&
+          hipMemcpy(film.data(), df.film, film.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+        std::fprintf(stderr, "film: copy failed\n");
+        return 1;
+      }
       if ((device_film ? write_pass_device_film(ctx, dev_develop, df, name, film.data(), sw, w, h, rgb)
                        : write_pass(ctx, dev_develop, name, film.data(), splat.data(), sw, w, h, rgb)) != 0) return 1;
     }

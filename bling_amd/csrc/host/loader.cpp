@@ -1492,6 +1492,15 @@ void bling_host_counts(const bling_host_scene* s, uint32_t* out6) {
   out6[0] = d.num_triangles; out6[1] = d.num_shapes; out6[2] = d.fractal.present ? 1u : 0u;
   out6[3] = d.num_prims; out6[4] = d.num_lights; out6[5] = bfeat::scene_features(&d);
 }
+float bling_host_sppm_splat_weight(const bling_render_config* cfg, int pass, int* sn_out) {
+  if (sn_out) *sn_out = 0;
+  if (!cfg || cfg->renderer != BLING_RENDERER_SPPM || pass < 1) return 0.f;
+  const int threads = std::max(1, cfg->sppm_threads);
+  const int sn = std::max(1, (int)std::ceil(std::sqrt((float)cfg->sppm_photons / (float)threads)));
+  if (sn_out) *sn_out = sn;
+  return 1.f / (float)((long long)threads * pass * sn * sn);
+}
+
 const char* bling_host_summary(const bling_host_scene* s) { return s ? s->b.summary.c_str() : ""; }
 void bling_host_free(bling_host_scene* s) { delete s; }
 const char* bling_host_last_error(void) { return g_err.c_str(); }

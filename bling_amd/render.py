@@ -22,6 +22,8 @@ DEFAULT_SEED = 0x0B11A6   # master seed of the benchmark
 
 
 # numpy view of bling_light_record (include/bling.h)
+SPPM_RECORD = np.dtype([("thread", "<u4"), ("photon", "<u4"), ("seq", "<u4"), ("depth", "<u4"), ("sx", "<i4"), ("sy", "<i4"),
+                        ("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("pad", "<u4")])
 LIGHT_RECORD = np.dtype([("photon", "<u4"), ("depth", "<u4"), ("sx", "<i4"), ("sy", "<i4"),
                          ("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("pad", "<u4")])
 
@@ -495,6 +497,42 @@ class Context:
         fl = (_ffi.SPLAT_ORDERED if ordered else 0) if flags is None else int(flags)
         _check(_ffi.hip().bling_mlt_pass_device(self._h, seed, pass_index, fl, C.c_void_p(ptr), C.byref(st)))
         return st
+
+    def sppm_pass_device(self, film, splat, seed=DEFAULT_SEED, pass_index=1, ordered=False, flags=None):
+        """bling_sppm_pass_device: one SPPM pass accumulated into a device film (float32, w * h * 4: W, X, Y, Z)
+        and a device splat image (float32, w * h * 3), which never visit the host; either may be None and is then
+        not produced.  ordered=True forms both in the reference's order without float atomics
+        (BLING_SPLAT_ORDERED): the same bits on every run.  Returns SppmStats."""
+        if self.job is None:
+            raise BlingError(-4, "no scene uploaded")
+        fptr = None if film is None else self._develop_tensor(film, "film", "float32", self.job.width * self.job.height * 4)
+        sptr = None if splat is None else self._splat_tensor(splat)
+        st = _ffi.SppmStats()
+        fl = (_ffi.SPLAT_ORDERED if ordered else 0) if flags is None else int(flags)
+        _check(_ffi.hip().bling_sppm_pass_device(self._h, seed, pass_index, fl, C.c_void_p(fptr), C.c_void_p(sptr), C.byref(st)))
+        return st
+
+    def sppm_records(self, seed=DEFAULT_SEED, pass_index=1, thread=0, first_photon=0, n_photons=None, cap=None):
+        """bling_debug_sppm_records: the splats of a range of one photon sampler's photons as a structured array
+        (thread, photon, seq, depth, sx, sy, x, y, z, pad), sorted by (photon, seq), from an eye pass of the call's
+        own for the context's current radii.  Without cap the buffer is sized by a first counting call; a given cap
+        that is too small raises."""
+        if n_photons is None:
+            cfg = self.job.config
+            threads = max(1, cfg.sppm_threads)
+            sn = max(1, int(np.ceil(np.sqrt(np.float32(cfg.sppm_photons) / np.float32(threads)))))
+            n_photons = sn * sn - first_photon
+        lib = _ffi.hip()
+        n = C.c_size_t()
+        if cap is None:
+            rc = lib.bling_debug_sppm_records(self._h, seed, pass_index, thread, first_photon, n_photons, None, 0, C.byref(n))
+            if rc != 0 and n.value == 0:
+                _check(rc)
+            cap = n.value
+        rec = np.zeros(cap, SPPM_RECORD)
+        _check(lib.bling_debug_sppm_records(self._h, seed, pass_index, thread, first_photon, n_photons,
+                                            rec.ctypes.data_as(C.POINTER(_ffi.SppmRecord)), cap, C.byref(n)))
+        return rec[:n.value]
 
     def splat_merge(self, records, splat):
         """bling_debug_splat_merge: the ordered merge alone, of a SPLAT_REC array into a device splat image."""

@@ -324,6 +324,51 @@ typedef struct bling_sppm_stats {
 int bling_sppm_pass(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, float* film_out, float* splat_out,
                     bling_sppm_stats* stats);
 
+/* bling_sppm_pass with both images in caller-owned device buffers: film_device
+ * holds W*H*4 floats (W, X, Y, Z) and splat_device W*H*3 floats (XYZ), both on device_ids[0] (e.g. torch
+ * tensors' data_ptr()); they are ACCUMULATED into and never copied to the host, and feed
+ * bling_film_develop_device directly.  Either may be NULL: that image is then not produced.  The pixel
+ * statistics stay in the context.  The call runs on the context's stream and returns after completion.
+ *   flags == 0: bling_sppm_pass's kernels and float atomics -- the same arithmetic, counters and statistics,
+ *     images that differ from its only in the order of their binary32 sums -- without the host staging.
+ *   BLING_SPLAT_ORDERED (below): no float atomic anywhere in the pass; both images are formed in the
+ *     reference's order (SPPM.hs:133-164, 424-460) and are the same on every run, whatever the launch
+ *     geometry, chunking or timing.
+ *     Film: each 16 x 16 extent tile's image starts at zero and receives the addSample of its pixels' eye
+ *     samples in (iy, ix) order; the tile images are then added into the film in tile order, film = film + tile
+ *     per channel.
+ *     Splats: each of the sppm_threads samplers k builds its own image from zero, adding its splats one at a
+ *     time by (photon n, then the order in which the photon's walk meets (vertex, hit point) pairs: depth,
+ *     then treeLookup's order); the samplers' images are then added in k order, splat = splat + image_k.  A
+ *     two-level sum: a flat fold over all the splats of a pixel gives other bits.
+ *     The statistics, the pixel statistics and the hit points equal the atomic mode's exactly.
+ *     A sampler's splats go through the record buffer of the ordered light tracer (its budget,
+ *     bling_debug_set_splat_budget): ascending photon ranges are merged one after another, a range whose
+ *     records exceed the budget is halved and run again (its rays, pairs and per-pixel counts are taken over
+ *     only once it fits), and a single photon that alone exceeds it is BLING_EINVAL (the film, the splats of
+ *     the samplers before it and the pixel statistics of no pass are then in an unspecified state: call
+ *     bling_sppm_reset).
+ * Errors: those of bling_sppm_pass; BLING_EINVAL for unknown flag bits and for a context of several devices. */
+int bling_sppm_pass_device(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, uint32_t flags, void* film_device,
+                           void* splat_device, bling_sppm_stats* stats);
+
+/* Parity hook: the splats of photons first_photon .. first_photon + n_photons - 1 of sampler `thread` of
+ * that pass, one record per splat, sorted by (photon, seq); seq is the running index of the photon's
+ * (vertex, hit point) pairs, counting every pair (also those whose splat falls outside the image or is
+ * dropped), depth the vertex (0 = first hit).  The call performs an eye pass and builds the hash ITSELF,
+ * for the context's CURRENT radii: to see a pass's records, call it before that pass (a pass updates the
+ * radii).  Nothing is accumulated into any image and the pixel statistics are not updated; the hit points
+ * and buckets of the diagnostics below become this call's.  *n receives the number of records; a capacity
+ * smaller than *n is BLING_EINVAL (with *n set): never a silent truncation. */
+typedef struct bling_sppm_record {
+    uint32_t thread, photon, seq, depth;
+    int32_t  sx, sy;           /* pixel (floor of the hit point's raster position)                */
+    float    x, y, z;          /* the XYZ the splat adds                                          */
+    uint32_t pad;
+} bling_sppm_record;
+int bling_debug_sppm_records(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, uint32_t thread, uint32_t first_photon,
+                             uint32_t n_photons, bling_sppm_record* records, size_t cap, size_t* n);
+
 /* The per-pixel statistics (PixelStats psR2 / psN, SPPM.hs:245-257) over the sample extent, in
  * sIdx order (windowPixels entries, written to *n_pixels); r2_out / n_out may be NULL. */
 int bling_sppm_pixel_stats(bling_ctx* ctx, float* r2_out, float* n_out, size_t* n_pixels);
@@ -452,7 +497,8 @@ int bling_debug_mlt_set_boot(bling_ctx* ctx, const float* I, uint32_t n);
  *     merges once a pass: 2 M records (M = mutations) beyond the budget are refused with BLING_EINVAL
  *     before any launch, the image untouched.
  * Errors: those of bling_light_pass / bling_mlt_pass, and BLING_EINVAL for unknown flag bits or a NULL
- * splat_device.  SPPM's splat image is not served. */
+ * splat_device.  SPPM's film and splat image are served by bling_sppm_pass_device (above), whose ordered
+ * sum has two levels. */
 #define BLING_SPLAT_ORDERED 1u
 int bling_light_pass_device(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, uint32_t flags, void* splat_device,
                             bling_light_stats* stats);

@@ -41,6 +41,11 @@ void bling_host_counts(const bling_host_scene* s, uint32_t* out6);
 /* Human-readable summary of the parsed scene (prettyPrint Scene, Scene.hs:28-35). */
 const char* bling_host_summary(const bling_host_scene* s);
 
+/* SPPM's splat weight of pass k (k >= 1): 1 / (threads * k * sn^2), sn = ceil (sqrt (photons / threads))
+ * in binary32 (Renderer/SPPM.hs:449, 460, 474) -- what getPixel applies to the photon image after pass k.
+ * *sn_out (may be NULL) receives sn.  0 for a scene whose renderer is not sppm or k < 1. */
+float bling_host_sppm_splat_weight(const bling_render_config* cfg, int pass, int* sn_out);
+
 void bling_host_free(bling_host_scene* s);
 
 const char* bling_host_last_error(void);
