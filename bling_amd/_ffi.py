@@ -24,6 +24,7 @@ PASS_TILE_IMAGES = 4       # BLING_PASS_TILE_IMAGES
 PASS_REGION_EVENTS = 8     # BLING_PASS_REGION_EVENTS (bling_render only)
 PASS_NO_MIS_CULL = 16      # BLING_PASS_NO_MIS_CULL
 PASS_NO_PIPELINE = 32      # BLING_PASS_NO_PIPELINE
+PASS_ORDERED_FILM = 64     # BLING_PASS_ORDERED_FILM
 
 
 class PassParams(C.Structure):

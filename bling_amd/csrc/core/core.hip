@@ -600,18 +600,48 @@ std::vector<TileDesc> pass_tiles(const DevScene& S, int rank, int world, int str
 // Film splat of a chunk's tiles: the register-window kernel for the filter widths the configs use,
 // the per-sample LDS-atomic kernel otherwise.  timg != NULL: the chunk's tile images into their slots.
 // td: the chunk's tile table on the device (n_tiles entries).
-void launch_film(bling_ctx* c, const WaveState& P, const TileDesc* td, unsigned n_tiles, float* film_dev, float* timg) {
+// ordered (BLING_PASS_ORDERED_FILM): the tile images in the reference's order, without atomics, always
+// into their slots (k_film_ordered: the window kernel for the square K = 3, 5, 7, else the generic one).
+void launch_film(bling_ctx* c, const WaveState& P, const TileDesc* td, unsigned n_tiles, float* film_dev, float* timg,
+                 bool ordered = false) {
   const float fw = c->S.filter_w, fh = c->S.filter_h;
   const int kx = 2 * (int)std::floor(0.5f + fw) + 1, ky = 2 * (int)std::floor(0.5f + fh) + 1;
   int sw, sh;
   tile_slot(c->S, &sw, &sh);
   hipStream_t s = c->stream;
+  if (ordered) {
+    if (!timg) throw std::logic_error("ordered film without tile images");
+    if (kx == ky && kx == 3) k_film_ordered<3><<<n_tiles, 256, 0, s>>>(c->dscene.p, P, td, timg, sw, sh);
+    else if (kx == ky && kx == 5) k_film_ordered<5><<<n_tiles, 256, 0, s>>>(c->dscene.p, P, td, timg, sw, sh);
+    else if (kx == ky && kx == 7) k_film_ordered<7><<<n_tiles, 256, 0, s>>>(c->dscene.p, P, td, timg, sw, sh);
+    else k_film_ordered<0><<<n_tiles, 256, 0, s>>>(c->dscene.p, P, td, timg, sw, sh);
+    return;
+  }
   if (kx == 5 && ky == 5)
     k_film_gather<5><<<n_tiles, 256 * film_split<5>(), 0, s>>>(c->dscene.p, P, td, film_dev, timg, sw, sh);
   else if (kx == 7 && ky == 7)
     k_film_gather<7><<<n_tiles, 256 * film_split<7>(), 0, s>>>(c->dscene.p, P, td, film_dev, timg, sw, sh);
   else
     k_film<<<n_tiles, 256, 0, s>>>(c->dscene.p, P, td, film_dev, timg, sw, sh);
+}
+
+// addTile in tile order (k_film_add_ordered) of the tile images of p's stride into a device film: one
+// rank's (rank >= 0, from `one`) or every rank's of p's world (rank < 0, ranks_dev: the buffers' device
+// pointers on the device)
+void add_tiles_ordered(bling_ctx* c, const bling_pass_params* p, int rank, const float* one, const float4* const* ranks_dev,
+                       float* film_dev) {
+  int sw, sh;
+  tile_slot(c->S, &sw, &sh);
+  const FilmOrderedSrc src{reinterpret_cast<const float4*>(one), ranks_dev, rank, std::max(1, p->shard_world), std::max(1, p->tile_stride)};
+  const size_t npix = (size_t)c->S.width * c->S.height;
+  k_film_add_ordered<<<(unsigned)((npix + 255) / 256), 256, 0, c->stream>>>(c->dscene.p, src, film_dev, sw, sh);
+  HIPCHK(hipGetLastError());
+}
+
+// BLING_PASS_ORDERED_FILM is served on single-device contexts
+void check_ordered(const bling_ctx* c, const bling_pass_params* p) {
+  if ((p->flags & BLING_PASS_ORDERED_FILM) && !c->peers.empty())
+    throw std::invalid_argument("BLING_PASS_ORDERED_FILM on a multi-device context");
 }
 
 struct PassPlan {                 // what render() settles before its first launch
@@ -622,6 +652,8 @@ struct PassPlan {                 // what render() settles before its first laun
   bool pipe = false;              // one wave, at least two tiles: two half-waves cut at a tile boundary, in flight together
   float* timg = nullptr;          // BLING_PASS_TILE_IMAGES: the tile images, slot_floats per tile
   size_t slot_floats = 0;
+  bool ordered = false;           // BLING_PASS_ORDERED_FILM: the film kernels write ordered tile images
+  bool add_film = false;          // ... into the context's own buffer (timg), added into the film after the last wave
   float* timg_at(size_t tile) const { return timg ? timg + tile * slot_floats : nullptr; }
 };
 
@@ -637,6 +669,15 @@ PassPlan plan_pass(bling_ctx* c, const bling_pass_params* p) {
   if (pl.timg && p->tiles_capacity < pl.tiles.size() * pl.slot_floats)
     throw std::invalid_argument("tiles_capacity " + std::to_string(p->tiles_capacity) + " floats < the " +
                                 std::to_string(pl.tiles.size() * pl.slot_floats) + " this shard's tile images need");
+  pl.ordered = (p->flags & BLING_PASS_ORDERED_FILM) != 0;
+  if (pl.ordered && !pl.timg) {
+    // a film pixel is covered by tiles of different waves: the pass keeps all its tile images and forms
+    // the film once, after the last wave
+    const size_t need = std::max<size_t>(1, pl.tiles.size() * pl.slot_floats);
+    if (c->pass_tiles.n < need) c->pass_tiles.alloc(need);
+    pl.timg = c->pass_tiles.p;
+    pl.add_film = true;
+  }
   uint32_t max_tile = 0;
   for (auto& t : pl.tiles) { pl.counts.push_back(t.count); pl.total += t.count; max_tile = std::max(max_tile, t.count); }
   size_t free_b = 0, total_b = 0;
@@ -697,7 +738,7 @@ void render_pair(bling_ctx* c, const bling_pass_params* p, const PassPlan& pl, c
       HIPCHK(hipEventRecord(c->half_done[h], hs[h]));
       HIPCHK(hipStreamWaitEvent(s, c->half_done[h], 0));
       if (h == 1) r.bounce.b.record(s);
-      launch_film(c, H[h].W, H[h].td, H[h].n_tiles, film_dev, pl.timg_at(h ? hc.cut : 0));
+      launch_film(c, H[h].W, H[h].td, H[h].n_tiles, film_dev, pl.timg_at(h ? hc.cut : 0), pl.ordered);
     }
     r.film_end.record(s);
     HIPCHK(hipGetLastError());
@@ -728,7 +769,9 @@ bling_stats stats_from_counters(const Counters& hc, bling_stats st, bool vertice
 }
 
 int render(bling_ctx* c, const bling_pass_params* p, float* film_dev, bling_stats* st) {
+  check_ordered(c, p);
   const PassPlan pl = plan_pass(c, p);
+  if (pl.add_film && !film_dev) throw std::invalid_argument("null argument");
   WaveState P = c->state();
   if (p->flags & BLING_PASS_NO_MIS_CULL) P.mis_cull = 0u;
   c->last_pass_waves = 0;
@@ -755,15 +798,22 @@ int render(bling_ctx* c, const bling_pass_params* p, float* film_dev, bling_stat
       else r.st.bounce_launches += (uint64_t)run_wave(c, P, w.off, p->seed, p->pass_index, (p->flags & BLING_PASS_TRAVERSAL_STATS) != 0, &r.tm);
     }
     r.bounce.b.record(s);
-    launch_film(c, P, c->tiles_dev.p, nt, film_dev, pl.timg_at(t0));
+    launch_film(c, P, c->tiles_dev.p, nt, film_dev, pl.timg_at(t0), pl.ordered);
     r.film_end.record(s);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));   // the tile table is reused by the next chunk
     wave_done(c, r, c->last_pass_waves + 1, w.off, 0, 0);
     t0 = w.t1;
   }
+  const EventPair add;
+  if (pl.add_film) {
+    add.a.record(s);
+    add_tiles_ordered(c, p, p->shard_rank, pl.timg, nullptr, film_dev);
+    add.b.record(s);
+  }
   pass.b.record(s);
   HIPCHK(hipEventSynchronize(pass.b));
+  if (pl.add_film) r.st.ms_film += add.elapsed_ms();
   Counters hc;
   HIPCHK(hipMemcpy(&hc, c->counters.p, sizeof hc, hipMemcpyDeviceToHost));
   std::memcpy(c->stream_bytes, hc.sb, sizeof c->stream_bytes);
@@ -807,6 +857,7 @@ void add_tiles(bling_ctx* c, const std::vector<std::pair<const std::vector<TileD
 // numCapabilities` of prender (Rendering.hs:111-140, :118) and its addTile merge.
 int render_fanout(bling_ctx* c, const bling_pass_params* p, float* film_dev, bling_stats* st) {
   if (c->peers.empty()) return render(c, p, film_dev, st);
+  check_ordered(c, p);
   if (p->flags & BLING_PASS_TILE_IMAGES) throw std::invalid_argument("BLING_PASS_TILE_IMAGES on a multi-device context");
   const int nd = 1 + (int)c->peers.size();
   const int world = std::max(1, p->shard_world), rank = p->shard_rank;
@@ -1100,7 +1151,11 @@ int bling_film_add_tiles(bling_ctx* c, const bling_pass_params* p, const void* t
     HIPCHK(hipSetDevice(c->device));
     const std::vector<TileDesc> tiles = pass_tiles(c->S, p->shard_rank, p->shard_world, p->tile_stride);
     check_tiles_capacity(c, p, tiles.size());
-    add_tiles(c, {{&tiles, static_cast<const float*>(tiles_device)}}, static_cast<float*>(film_device));
+    check_ordered(c, p);
+    if (p->flags & BLING_PASS_ORDERED_FILM)
+      add_tiles_ordered(c, p, p->shard_rank, static_cast<const float*>(tiles_device), nullptr, static_cast<float*>(film_device));
+    else
+      add_tiles(c, {{&tiles, static_cast<const float*>(tiles_device)}}, static_cast<float*>(film_device));
     HIPCHK(hipStreamSynchronize(c->stream));
     return BLING_OK;
   });
@@ -1120,7 +1175,15 @@ int bling_film_add_shards(bling_ctx* c, const bling_pass_params* p, const void* 
       check_tiles_capacity(c, p, tiles[r].size());
       sets.emplace_back(&tiles[r], static_cast<const float*>(tiles_devices[r]));
     }
-    add_tiles(c, sets, static_cast<float*>(film_device));
+    check_ordered(c, p);
+    if (p->flags & BLING_PASS_ORDERED_FILM) {
+      std::vector<const float4*> bufs(world);
+      for (int r = 0; r < world; ++r) bufs[r] = static_cast<const float4*>(tiles_devices[r]);
+      c->rank_bufs.upload(bufs.data(), bufs.size());
+      add_tiles_ordered(c, p, -1, nullptr, c->rank_bufs.p, static_cast<float*>(film_device));
+    } else {
+      add_tiles(c, sets, static_cast<float*>(film_device));
+    }
     HIPCHK(hipStreamSynchronize(c->stream));
     return BLING_OK;
   });
@@ -1207,13 +1270,14 @@ int region_pass(bling_ctx* c, const bling_pass_params& p, bling_stats* st, std::
 }
 // addTile of one tile image slot (the layout film_flush writes) into a host film: k_add_tiles' rule
 // (zero pixels and pixels past the film skipped), one tile at a time in the caller's order
-void add_tile_host(float* film, int width, int height, const float* img, int ox, int oy, int sw, int sh) {
+// (all: zero pixels are added too, as the ordered film does: film = film + tile for every covered pixel)
+void add_tile_host(float* film, int width, int height, const float* img, int ox, int oy, int sw, int sh, bool all) {
   for (int y = 0; y < sh; ++y)
     for (int x = 0; x < sw; ++x) {
       const int gx = ox + x, gy = oy + y;
       if (gx >= width || gy >= height) continue;
       const float* v = img + 4 * ((size_t)y * sw + x);
-      if (v[0] == 0.f && v[1] == 0.f && v[2] == 0.f && v[3] == 0.f) continue;
+      if (!all && v[0] == 0.f && v[1] == 0.f && v[2] == 0.f && v[3] == 0.f) continue;
       float* o = film + 4 * ((size_t)gy * width + gx);
       o[0] += v[0]; o[1] += v[1]; o[2] += v[2]; o[3] += v[3];
     }
@@ -1248,7 +1312,7 @@ int bling_render(bling_ctx* c, const bling_pass_params* p, float* film_out, blin
         (void)report(user, &rs);
         if (exact)                                                    // addTile of this window (Rendering.hs:133)
           add_tile_host(film_out, c->S.width, c->S.height, rimages.data() + k * (size_t)rsw * rsh * 4,
-                        std::max(0, t.x0), std::max(0, t.y0), rsw, rsh);
+                        std::max(0, t.x0), std::max(0, t.y0), rsw, rsh, (pp.flags & BLING_PASS_ORDERED_FILM) != 0);
         const bling_progress sa{BLING_PROGRESS_SAMPLES_ADDED, (int32_t)pp.pass_index, film_out, 1.f, nullptr,
                                 {t.x0, t.x1, t.y0, t.y1}};
         (void)report(user, &sa);

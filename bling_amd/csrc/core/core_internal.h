@@ -316,6 +316,7 @@ struct bling_ctx {
   std::vector<std::unique_ptr<bling_ctx>> peers;
   DBuf<float> pass_tiles;          // this device's tile images of the pass (BLING_PASS_TILE_IMAGES)
   DBuf<TileSrc> tile_src;          // the merge's per-tile sources (k_add_tiles)
+  DBuf<const float4*> rank_bufs;   // the ordered merge's per-rank tile-image buffers (k_film_add_ordered)
   std::vector<std::unique_ptr<DBuf<float>>> stage;  // primary: landing buffer of peer j's tile images
   MergeState merge;                // the ordered splat merge (splat_merge.h)
 

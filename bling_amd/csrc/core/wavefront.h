@@ -1931,4 +1931,148 @@ static __global__ __launch_bounds__(256) void k_add_tiles(const TileSrc* __restr
   }
 }
 
+// ------------------------------------------------------------------ ordered film (BLING_PASS_ORDERED_FILM)
+// The tile image without atomics, in the reference's order.  One block per tile; a thread owns up to NP
+// pixels of the tile's slot (sw x sh, the layout film_flush writes) and adds to each, in registers from
+// +0, the filtered contributions of the tile's samples in (iy, ix, n) order, whatever the slot order of
+// the pass -- k_film's pixel ranges, table indices, clipping, r.w == 0 skip and trap T12, with the loops
+// turned inside out (addSample, Image.hs:250-299).  Sample records are staged through LDS in chunks that
+// are contiguous in that order: a run of whole source pixels (FILM_ORD_CHUNK / spp of them; one pixel's
+// samples in runs of FILM_ORD_CHUNK where spp is larger), laid out sample-major within the chunk so
+// that neighbouring lanes, which read neighbouring source pixels, read neighbouring records.
+//   K = 3, 5, 7 (square filters, K = 2 floor(0.5 + fw) + 1): a pixel visits only the source pixels of
+//     its own K x K window -- a source pixel outside it reaches the pixel in neither k_film_gather (whose
+//     thread owns exactly that window, the rounded-up ix + ox included) nor here; K^2 spp visits a pixel.
+//   K = 0: every other filter; a pixel visits all of the tile's samples.
+constexpr int FILM_ORD_CHUNK = 1024;   // 24 KiB of records in LDS: six blocks a CU
+template <int K>
+constexpr int film_ord_pixels() { return K ? ((15 + K / 2) * (15 + K / 2) + 255) / 256 : FILM_TILE_MAX * FILM_TILE_MAX / 256; }
+template <int K>
+static __global__ __launch_bounds__(256) void k_film_ordered(const DevScene* __restrict__ Sptr, WaveState W,
+                                                      const TileDesc* __restrict__ tiles, float* __restrict__ timg,
+                                                      int sw, int sh) {
+  __shared__ float4 sres[FILM_ORD_CHUNK];
+  __shared__ float2 simg[FILM_ORD_CHUNK];
+  __shared__ float tbl[256];
+  constexpr int R = K / 2;
+  constexpr int NP = film_ord_pixels<K>();
+  const DevScene& S = *Sptr;
+  const TileDesc td = tiles[blockIdx.x];
+  const float fw = S.filter_w, fh = S.filter_h;
+  const int ox = max(0, td.x0), oy = max(0, td.y0);
+  const int w = td.x1 - ox + (int)floorf(0.5f + fw), h = td.y1 - oy + (int)floorf(0.5f + fh);
+  tbl[threadIdx.x] = S.filter_table[threadIdx.x];
+  const float ifw = 1.f / fw, ifh = 1.f / fw;                            // trap T12
+  const int tw = td.x1 - td.x0 + 1;
+  const uint32_t npix = (uint32_t)(tw * (td.y1 - td.y0 + 1)), spp = (uint32_t)S.spp;
+  int px[NP], py[NP];
+  bool own[NP];
+  float acc[NP][4];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const int q = (int)threadIdx.x + 256 * p, lx = q % sw, ly = q / sw;
+    own[p] = q < sw * sh && lx < w && ly < h && lx + ox < S.width && ly + oy < S.height;
+    px[p] = ox + lx; py[p] = oy + ly;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[p][c] = 0.f;
+  }
+  // one sample's contribution to the pixel (x, y): a = a + w, a = a + (v * w), the product rounded first
+  auto add = [&](uint32_t j, int x, int y, float* a) {
+    const float4 r = sres[j];
+    if (r.w == 0.f) return;
+    const float2 im = simg[j];
+    const float dx = im.x - 0.5f, dy = im.y - 0.5f;
+    const int x0 = max(ox, (int)ceilf(dx - fw)), x1 = min(ox + w - 1, (int)floorf(dx + fw));
+    const int y0 = max(oy, (int)ceilf(dy - fh)), y1 = min(oy + h - 1, (int)floorf(dy + fh));
+    if (x < x0 || x > x1 || y < y0 || y > y1) return;
+    const int fy = min((int)floorf(fabsf(((float)y - dy) * ifh * 16.f)), 15);
+    const int fx = min((int)floorf(fabsf(((float)x - dx) * ifw * 16.f)), 15);
+    const float fltw = tbl[fy * 16 + fx];
+    const float vx = r.x * fltw, vy = r.y * fltw, vz = r.z * fltw;
+    a[0] = a[0] + fltw; a[1] = a[1] + vx; a[2] = a[2] + vy; a[3] = a[3] + vz;
+  };
+  const uint32_t cp = max(1u, (uint32_t)FILM_ORD_CHUNK / spp), cn = min(spp, (uint32_t)FILM_ORD_CHUNK);
+  for (uint32_t pt0 = 0; pt0 < npix; pt0 += cp) {
+    const uint32_t np = min(cp, npix - pt0);                            // source pixels pt0 .. pt0 + np - 1
+    for (uint32_t n0 = 0; n0 < spp; n0 += cn) {
+      const uint32_t nn = min(cn, spp - n0);                            // their samples n0 .. n0 + nn - 1
+      __syncthreads();                                                  // the previous chunk is consumed (first: tbl is written)
+      for (uint32_t e = threadIdx.x; e < np * nn; e += blockDim.x) {
+        const uint32_t nl = e / np, pt = pt0 + (e - nl * np), n = n0 + nl;
+        const uint32_t slot = td.offset + (S.sample_major ? n * npix + pt : pt * spp + n);   // k_raygen's order
+        sres[e] = W.result[slot];
+        simg[e] = W.img[slot];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        if (!own[p]) continue;
+        const int x = px[p], y = py[p];
+        float a[4] = {acc[p][0], acc[p][1], acc[p][2], acc[p][3]};
+        if (K == 0) {
+          for (uint32_t pl = 0; pl < np; ++pl)
+            for (uint32_t nl = 0; nl < nn; ++nl) add(nl * np + pl, x, y, a);
+        } else {
+          const int pt1 = (int)(pt0 + np) - 1;
+          const int ya = max(max(y - R, td.y0), td.y0 + (int)pt0 / tw), yb = min(min(y + R, td.y1), td.y0 + pt1 / tw);
+          const int xa = max(x - R, td.x0), xb = min(x + R, td.x1);
+          for (int iy = ya; iy <= yb; ++iy)
+            for (int ix = xa; ix <= xb; ++ix) {
+              const int pt = (iy - td.y0) * tw + (ix - td.x0);
+              if (pt < (int)pt0 || pt > pt1) continue;
+              const uint32_t pl = (uint32_t)pt - pt0;
+              for (uint32_t nl = 0; nl < nn; ++nl) add(nl * np + pl, x, y, a);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[p][c] = a[c];
+      }
+    }
+  }
+  float4* slot = reinterpret_cast<float4*>(timg) + (size_t)blockIdx.x * sw * sh;
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const int q = (int)threadIdx.x + 256 * p;
+    if (q < sw * sh) slot[q] = own[p] ? make_float4(acc[p][0], acc[p][1], acc[p][2], acc[p][3]) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+// addTile in tile order (Image.hs:178-199): one thread per film pixel adds, film = film + tile per
+// channel, zero values too, the values of the selected tile images that cover it in ascending tile
+// index.  The covering tiles follow from the grid: tile (tx, ty) of splitWindow starts at (ex0 + 16 tx,
+// ey0 + 16 ty) and its image spans [max(0, x0), x1 + floor(0.5 + fw) - 1], so along an axis at most
+// (apron + 30) / 16 tiles reach a pixel.  Tile k (row-major) is selected iff k % stride == 0; it then
+// lives in rank (k / stride) % world at slot (k / stride) / world of that rank's buffer.  rank >= 0:
+// that rank's tiles only, from `one`; rank < 0: every rank's, from ranks[0 .. world - 1].
+struct FilmOrderedSrc { const float4* one; const float4* const* ranks; int rank, world, stride; };
+static __global__ __launch_bounds__(256) void k_film_add_ordered(const DevScene* __restrict__ Sptr, FilmOrderedSrc src,
+                                                          float* __restrict__ film, int sw, int sh) {
+  const DevScene& S = *Sptr;
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= (uint32_t)S.width * (uint32_t)S.height) return;
+  const int gx = (int)(p % (uint32_t)S.width), gy = (int)(p / (uint32_t)S.width);
+  const int rx = (int)floorf(0.5f + S.filter_w), ry = (int)floorf(0.5f + S.filter_h);
+  const int ntx = (S.ext_w + 15) / 16, nty = (S.ey1 - S.ey0 + 16) / 16;
+  const int txh = min((gx - S.ex0) / 16, ntx - 1), tyh = min((gy - S.ey0) / 16, nty - 1);   // the last tile that starts at or before the pixel
+  const int txl = max(0, txh - ((rx + 30) / 16 - 1)), tyl = max(0, tyh - ((ry + 30) / 16 - 1));
+  float* o = film + 4 * (size_t)p;
+  float4 f = make_float4(o[0], o[1], o[2], o[3]);
+  for (int ty = tyl; ty <= tyh; ++ty) {
+    const int y0 = S.ey0 + 16 * ty, y1 = min(y0 + 15, S.ey1), oy = max(0, y0);
+    if (gy < oy || gy >= oy + (y1 - oy + ry)) continue;
+    for (int tx = txl; tx <= txh; ++tx) {
+      const int x0 = S.ex0 + 16 * tx, x1 = min(x0 + 15, S.ex1), ox = max(0, x0);
+      if (gx < ox || gx >= ox + (x1 - ox + rx)) continue;
+      const int k = ty * ntx + tx;
+      if (k % src.stride != 0) continue;
+      const int m = k / src.stride, r = m % src.world;
+      if (src.rank >= 0 && r != src.rank) continue;
+      const float4* buf = src.rank >= 0 ? src.one : src.ranks[r];
+      const float4 v = buf[(size_t)(m / src.world) * sw * sh + (gx - ox) + (gy - oy) * sw];
+      f.x = f.x + v.x; f.y = f.y + v.y; f.z = f.z + v.z; f.w = f.w + v.w;
+    }
+  }
+  o[0] = f.x; o[1] = f.y; o[2] = f.z; o[3] = f.w;
+}
+
 }  // namespace bd

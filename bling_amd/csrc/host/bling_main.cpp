@@ -3,11 +3,14 @@
 // pass-NNNNN.png and .hdr at PassDone) over the host loader and the MI355X core.
 //
 //   bling <scene.bling> [--overrides "image=W,H;..."] [--passes N] [--out prefix] [--device D]
-//         [--develop host|device] [--splat atomic|ordered]
+//         [--develop host|device] [--splat atomic|ordered] [--film atomic|ordered]
 // --develop device makes each written pass's 8-bit and RGBE pixels on the device (bling_film_develop)
 // and hands them to the encoders; the default, host, develops with the host library.  Same files.
 // --splat ordered (light tracer, Metropolis and SPPM scenes) adds every pixel's splats in the reference's order
 // (BLING_SPLAT_ORDERED): the same files on every run; the default, atomic, adds them with float atomics.
+// --film ordered (sampler scenes; the environment's BLING_FILM_ORDERED=1 means the same) forms every pass's film in
+// the reference's order without float atomics (BLING_PASS_ORDERED_FILM): the same files on every run.  The splat
+// renderers refuse it: their switch is --splat.
 // With --develop device, or --splat ordered, such a scene's splat image (and an SPPM scene's film) lives on
 // the device for the whole run (bling_light_pass_device / bling_mlt_pass_device / bling_sppm_pass_device);
 // --develop device then develops it there (bling_film_develop_device) and only the developed pixels come back.
@@ -101,7 +104,7 @@ int write_pass(bling_ctx* ctx, bool on_device, const std::string& name, const fl
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    std::fprintf(stderr, "usage: %s scene.bling [--overrides S] [--passes N] [--out prefix] [--device D] [--develop host|device] [--splat atomic|ordered]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s scene.bling [--overrides S] [--passes N] [--out prefix] [--device D] [--develop host|device] [--splat atomic|ordered] [--film atomic|ordered]\n", argv[0]);
     return 2;
   }
   const char* scene = argv[1];
@@ -109,6 +112,8 @@ int main(int argc, char** argv) {
   const char* out = "pass";
   int passes = 1, device = 0;
   bool dev_develop = false, ordered = false;
+  const char* film_env = std::getenv("BLING_FILM_ORDERED");
+  bool film_ordered = film_env && film_env[0] == '1';
   for (int i = 2; i + 1 < argc; i += 2) {
     if (!std::strcmp(argv[i], "--overrides")) ov = argv[i + 1];
     else if (!std::strcmp(argv[i], "--passes")) passes = std::atoi(argv[i + 1]);
@@ -126,6 +131,12 @@ int main(int argc, char** argv) {
         return 2;
       }
       ordered = !std::strcmp(argv[i + 1], "ordered");
+    } else if (!std::strcmp(argv[i], "--film")) {
+      if (std::strcmp(argv[i + 1], "atomic") && std::strcmp(argv[i + 1], "ordered")) {
+        std::fprintf(stderr, "--film takes atomic or ordered, not %s\n", argv[i + 1]);
+        return 2;
+      }
+      film_ordered = !std::strcmp(argv[i + 1], "ordered");
     }
   }
   bling_host_scene* hs = nullptr;
@@ -141,6 +152,10 @@ int main(int argc, char** argv) {
   std::vector<float> film((size_t)w * h * 4, 0.f), rgb((size_t)w * h * 3);
   const bool splats = d->config.renderer == BLING_RENDERER_LIGHT || d->config.renderer == BLING_RENDERER_METROPOLIS ||
                       d->config.renderer == BLING_RENDERER_SPPM;
+  if (splats && film_ordered) {
+    std::fprintf(stderr, "--film ordered is for sampler scenes; this scene's renderer splats: use --splat ordered\n");
+    return 2;
+  }
   const bool device_film = splats && (dev_develop || ordered);
   const uint32_t splat_flags = ordered ? BLING_SPLAT_ORDERED : 0u;
   DeviceFilm df;
@@ -222,7 +237,7 @@ int main(int argc, char** argv) {
     return 0;
   }
   for (int p = 1; p <= passes; ++p) {
-    bling_pass_params pp{0x0B11A6u, (uint32_t)p, 0, 1, 1, 0};
+    bling_pass_params pp{0x0B11A6u, (uint32_t)p, 0, 1, 1, 0, film_ordered ? BLING_PASS_ORDERED_FILM : 0u};
     bling_stats st;
     if (bling_render_pass(ctx, &pp, film.data(), &st) != 0) { std::fprintf(stderr, "%s\n", bling_last_error()); return 1; }
     uint64_t rays = st.rays_camera + st.rays_continuation + st.rays_mis + st.rays_shadow;

@@ -78,28 +78,36 @@ class Context:
         self.job = job
 
     def render_pass(self, seed=DEFAULT_SEED, pass_index=0, shard=(0, 1), tile_stride=1, chunk_paths=0,
-                    film: np.ndarray | None = None, flags=0):
-        """One pass into a host film (accumulated). Returns (film, Stats)."""
+                    film: np.ndarray | None = None, flags=0, ordered=False):
+        """One pass into a host film (accumulated). Returns (film, Stats).  ordered=True forms the film in
+        the reference's order without float atomics (BLING_PASS_ORDERED_FILM): the same bits on every run,
+        however the pass is cut, equal to the CPU restatement's film."""
         job = self.job
         if film is None:
             film = np.zeros(job.width * job.height * 4, np.float32)
-        pp = _ffi.PassParams(seed, pass_index, shard[0], shard[1], tile_stride, chunk_paths, flags)
+        pp = _ffi.PassParams(seed, pass_index, shard[0], shard[1], tile_stride, chunk_paths, flags | self._ordered(ordered))
         st = _ffi.Stats()
         _check(_ffi.hip().bling_render_pass(self._h, C.byref(pp), _ffi.f32ptr(film), C.byref(st)))
         return film, st
 
+    @staticmethod
+    def _ordered(ordered):
+        return _ffi.PASS_ORDERED_FILM if ordered else 0
+
     def render_loop(self, report, seed=DEFAULT_SEED, first_pass=1, film: np.ndarray | None = None, shard=(0, 1),
-                    tile_stride=1, regions=None):
+                    tile_stride=1, regions=None, ordered=False):
         """bling_render: passes first_pass, first_pass + 1, ... into a host film until report(pass,
         film, stats) returns False (prender's onePass loop with its ProgressReporter,
         Rendering.hs:127-140); stats is that pass's own bling_stats as a dict.  With regions (a
         callable), every pass first reports prender's per-window events as regions(kind, pass,
         (x0, x1, y0, y1), film) with kind "region_started" (film None) or "samples_added"
-        (BLING_PASS_REGION_EVENTS).  Returns (film, Stats summed over the passes)."""
+        (BLING_PASS_REGION_EVENTS).  ordered=True: every pass's film, and with regions every
+        samples_added film, is the ordered one (BLING_PASS_ORDERED_FILM).  Returns (film, Stats summed
+        over the passes)."""
         job = self.job
         if film is None:
             film = np.zeros(job.width * job.height * 4, np.float32)
-        flags = _ffi.PASS_REGION_EVENTS if regions is not None else 0
+        flags = (_ffi.PASS_REGION_EVENTS if regions is not None else 0) | self._ordered(ordered)
         pp = _ffi.PassParams(seed, first_pass, shard[0], shard[1], tile_stride, 0, flags)
         st = _ffi.Stats()
         err = []
@@ -182,9 +190,10 @@ class Context:
         return {k: (int(out[2 * i]), int(out[2 * i + 1])) for i, k in enumerate(_ffi.STREAM_NAMES)}
 
     def render_pass_device(self, film_ptr: int, seed=DEFAULT_SEED, pass_index=0, shard=(0, 1), tile_stride=1,
-                           chunk_paths=0, flags=0):
-        """One pass accumulated into a device film (e.g. ``torch_tensor.data_ptr()``)."""
-        pp = _ffi.PassParams(seed, pass_index, shard[0], shard[1], tile_stride, chunk_paths, flags)
+                           chunk_paths=0, flags=0, ordered=False):
+        """One pass accumulated into a device film (e.g. ``torch_tensor.data_ptr()``); ordered as
+        render_pass's."""
+        pp = _ffi.PassParams(seed, pass_index, shard[0], shard[1], tile_stride, chunk_paths, flags | self._ordered(ordered))
         st = _ffi.Stats()
         _check(_ffi.hip().bling_render_pass_device(self._h, C.byref(pp), C.c_void_p(film_ptr), C.byref(st)))
         return st
@@ -221,30 +230,34 @@ class Context:
         return int(buf), int(capacity)
 
     def render_pass_tiles(self, tiles, seed=DEFAULT_SEED, pass_index=0, shard=(0, 1), tile_stride=1,
-                          chunk_paths=0, flags=0, tiles_capacity=None):
+                          chunk_paths=0, flags=0, tiles_capacity=None, ordered=False):
         """One pass written as tile images into a device buffer (BLING_PASS_TILE_IMAGES, layout
         tile_layout) instead of a film -- the per-rank half of the multi-GPU merge.  tiles: a device
-        tensor, or a raw pointer with tiles_capacity (floats)."""
+        tensor, or a raw pointer with tiles_capacity (floats).  ordered=True: the slots hold the ordered
+        tile images (BLING_PASS_ORDERED_FILM)."""
         ptr, cap = self._tiles_buf(tiles, tiles_capacity)
         pp = _ffi.PassParams(seed, pass_index, shard[0], shard[1], tile_stride, chunk_paths,
-                             flags | _ffi.PASS_TILE_IMAGES, C.c_void_p(ptr), cap)
+                             flags | _ffi.PASS_TILE_IMAGES | self._ordered(ordered), C.c_void_p(ptr), cap)
         st = _ffi.Stats()
         _check(_ffi.hip().bling_render_pass_device(self._h, C.byref(pp), None, C.byref(st)))
         return st
 
-    def film_add_tiles(self, tiles, film_ptr: int, shard=(0, 1), tile_stride=1, tiles_capacity=None):
-        """bling_film_add_tiles: addTile of one shard's tile images into a device film."""
+    def film_add_tiles(self, tiles, film_ptr: int, shard=(0, 1), tile_stride=1, tiles_capacity=None, ordered=False):
+        """bling_film_add_tiles: addTile of one shard's tile images into a device film; ordered=True adds
+        them per pixel in tile order, without atomics."""
         ptr, cap = self._tiles_buf(tiles, tiles_capacity)
-        pp = _ffi.PassParams(0, 0, shard[0], shard[1], tile_stride, 0, 0, None, cap)
+        pp = _ffi.PassParams(0, 0, shard[0], shard[1], tile_stride, 0, self._ordered(ordered), None, cap)
         _check(_ffi.hip().bling_film_add_tiles(self._h, C.byref(pp), C.c_void_p(ptr), C.c_void_p(film_ptr)))
 
-    def film_add_shards(self, tiles_list, film_ptr: int, tile_stride=1, tiles_capacity=None):
+    def film_add_shards(self, tiles_list, film_ptr: int, tile_stride=1, tiles_capacity=None, ordered=False):
         """bling_film_add_shards: every rank's tile images (rank r's buffer tiles_list[r]) into a
         device film in one launch -- rank 0's merge after the gather.  The capacity checked against
-        each rank's layout is the smallest buffer's (tensors), or tiles_capacity (raw pointers)."""
+        each rank's layout is the smallest buffer's (tensors), or tiles_capacity (raw pointers).
+        ordered=True adds the union of all ranks' tiles per pixel in global tile order: with ordered tile
+        images the film equals the single-rank ordered film bit for bit."""
         world = len(tiles_list)
         bufs = [self._tiles_buf(b, tiles_capacity) for b in tiles_list]
-        pp = _ffi.PassParams(0, 0, 0, world, tile_stride, 0, 0, None, min(c for _, c in bufs))
+        pp = _ffi.PassParams(0, 0, 0, world, tile_stride, 0, self._ordered(ordered), None, min(c for _, c in bufs))
         arr = (C.c_void_p * world)(*[C.c_void_p(p) for p, _ in bufs])
         _check(_ffi.hip().bling_film_add_shards(self._h, C.byref(pp), arr, C.c_void_p(film_ptr)))
 
@@ -580,9 +593,10 @@ class Progress:
 class SamplerRenderer:
     """``SamplerRenderer`` with the path integrator (Rendering.hs:111-140) on the MI355X core."""
 
-    def __init__(self, device: int = 0, seed: int = DEFAULT_SEED):
+    def __init__(self, device: int = 0, seed: int = DEFAULT_SEED, ordered: bool = False):
         self.device = device
         self.seed = seed
+        self.ordered = ordered       # BLING_PASS_ORDERED_FILM on every pass
 
     def render(self, job: Job, report) -> np.ndarray:
         """Passes 1, 2, ... through bling_render (the core's own pass loop) until the reporter
@@ -591,7 +605,7 @@ class SamplerRenderer:
         ctx.upload(job)
         report(Progress("Started"))
         film, _ = ctx.render_loop(lambda p, f, st: bool(report(Progress("PassDone", p, f, st))), seed=self.seed,
-                                  first_pass=1)
+                                  first_pass=1, ordered=self.ordered)
         ctx.close()
         return film
 
@@ -712,11 +726,12 @@ RENDERER_LIGHT = 3   # BLING_RENDERER_LIGHT (include/bling_scene.h)
 RENDERER_METROPOLIS = 4   # BLING_RENDERER_METROPOLIS
 
 
-def render(job: Job, passes: int = 1, device: int = 0, seed: int = DEFAULT_SEED) -> np.ndarray:
+def render(job: Job, passes: int = 1, device: int = 0, seed: int = DEFAULT_SEED, ordered: bool = False) -> np.ndarray:
     """Render `passes` progressive passes (the commented bling CLI harness renders exactly one,
     src/cmdline/Main.hs:15-26).  A sampler job returns its film (W, X, Y, Z); a `light` job, which
     only splats, returns the RGB image (h, w, 3) of its accumulated splats with the weight
-    1 / (passes * passPhotons)."""
+    1 / (passes * passPhotons).  ordered: the sampler renderer's ordered film (the splat renderers have
+    their own switch and ignore it)."""
     count = {"n": 0}
 
     def rep(pr: Progress) -> bool:
@@ -741,4 +756,4 @@ def render(job: Job, passes: int = 1, device: int = 0, seed: int = DEFAULT_SEED)
 
         film, splat = MetropolisRenderer(device, seed).render(job, rep_mlt)
         return film_splat_to_rgb(film, splat, np.float32(last["sw"]), job.width, job.height)
-    return SamplerRenderer(device, seed).render(job, rep)
+    return SamplerRenderer(device, seed, ordered).render(job, rep)

@@ -76,6 +76,23 @@ typedef struct bling_pass_params {
  * other's traversal share the device.  Every sample's arithmetic is the same either way; only the
  * order of the film's float additions differs.  The switch is for A/B measurements and the tests. */
 #define BLING_PASS_NO_PIPELINE     32u
+/* The film of the `sampler` renderer in the reference's order, without a float atomic: the same bits on
+ * every run, however the pass is cut into waves, and equal to the CPU restatement's.  Every tile's
+ * mkImageTile image (Image.hs:108-120) is formed per pixel and channel from +0 by adding the tile's
+ * contributing samples one at a time in (iy, ix, n) order -- a = a + w for W, a = a + (v * w) for X, Y, Z,
+ * the product rounded first -- whatever the slot order of the pass (addSample, Image.hs:250-299); the film
+ * then becomes film = film + tile_k per channel for every selected tile whose image covers the pixel, in
+ * ascending tile index, zero values included (addTile, Image.hs:178-199).  The incoming film is the first
+ * operand, so accumulated passes stay ordered.  Honoured by bling_render_pass, bling_render_pass_device,
+ * bling_render (with BLING_PASS_REGION_EVENTS every SamplesAdded film is ordered too), a
+ * BLING_PASS_TILE_IMAGES pass (the slots hold the ordered tile images), bling_film_add_tiles (that
+ * shard's tiles in tile order) and bling_film_add_shards (the union of all ranks' tiles in global tile
+ * order: the film of a gathered multi-rank pass equals the single-rank ordered film bit for bit).
+ * The pass keeps all its tile images until the last wave: n_tiles * slot_w * slot_h * 16 bytes of device
+ * memory (bling_pass_tile_layout; the caller's buffer with BLING_PASS_TILE_IMAGES).  Single-device
+ * contexts only: a context of several devices refuses the flag with BLING_EINVAL.  The splat renderers
+ * have their own switch (BLING_SPLAT_ORDERED). */
+#define BLING_PASS_ORDERED_FILM    64u
 
 typedef struct bling_stats {
     uint64_t camera_samples;   /* paths started                                               */
