@@ -25,7 +25,7 @@ HOST_SRC := bling_amd/csrc/host/loader.cpp
 HOST_HDR := bling_amd/csrc/host/hmath.h bling_amd/csrc/common/sky_model.h bling_amd/csrc/common/scene_features.h \
             bling_amd/csrc/common/spectral_data.h bling_amd/csrc/common/perlin.h include/bling_scene.h include/bling_host.h \
             bling_amd/csrc/common/image_tex.h bling_amd/csrc/common/cr_math.h bling_amd/csrc/host/image_io.h \
-            bling_amd/csrc/common/gamma_table.h
+            bling_amd/csrc/common/gamma_table.h bling_amd/csrc/common/image_sample.h
 CORE_SRC := $(wildcard bling_amd/csrc/core/*.hip) $(wildcard bling_amd/csrc/core/*.cpp)
 # STUB (experiment builds only) is part of the object directory: stubbed units never mix with real ones
 ifneq ($(strip $(STUB)),)
@@ -39,7 +39,7 @@ CORE_HDR := $(wildcard bling_amd/csrc/core/*.h) bling_amd/csrc/common/sky_model.
             bling_amd/csrc/common/spectral_data.h bling_amd/csrc/common/counter_rng.h include/bling.h include/bling_scene.h \
             bling_amd/csrc/common/scene_features.h bling_amd/csrc/common/perlin.h bling_amd/csrc/common/cr_math.h \
             bling_amd/csrc/common/fast_cr.h bling_amd/csrc/common/cellnoise.h bling_amd/csrc/common/image_tex.h \
-            bling_amd/csrc/common/gamma_table.h
+            bling_amd/csrc/common/gamma_table.h bling_amd/csrc/common/image_sample.h
 REF_HDR  := $(wildcard tests/ref/*.h)
 ORA_SRC  := $(wildcard oracle/*.cpp)
 ORA_HDR  := $(wildcard oracle/*.h) include/bling_scene.h bling_amd/csrc/common/perlin.h bling_amd/csrc/common/cr_math.h \
@@ -114,7 +114,7 @@ $(LIBDIR)/libbling_hip.so: $(CORE_OBJ)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(CORE_OBJ)
 
 $(LIBDIR)/bling: bling_amd/csrc/host/bling_main.cpp $(LIBDIR)/libbling_host.so $(LIBDIR)/libbling_hip.so
-	$(CXX) -O2 -std=c++17 -o $@ bling_amd/csrc/host/bling_main.cpp -I include -I $(ROCM)/include -D__HIP_PLATFORM_AMD__ \
+	$(CXX) -O2 -std=c++17 -ffp-contract=off -o $@ bling_amd/csrc/host/bling_main.cpp -I include -I $(ROCM)/include -D__HIP_PLATFORM_AMD__ \
 	   -L$(LIBDIR) -lbling_host -lbling_hip -L$(ROCM)/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,$(ROCM)/lib
 
 $(LIBDIR)/libbling_mathcheck.so: bling_amd/csrc/check/mathcheck.hip bling_amd/csrc/common/fast_cr.h bling_amd/csrc/common/cr_math.h

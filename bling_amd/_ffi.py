@@ -124,6 +124,29 @@ class DevelopParams(C.Structure):
     _fields_ = [("format", C.c_int32), ("splat_weight", C.c_float), ("window", C.c_int32 * 4)]
 
 
+FILTER_KINDS = {"box": 0, "gauss": 1, "sinc": 2, "mitchell": 3, "triangle": 4}   # BLING_FILTER_*
+IMAGE_OPS = {"add": 0, "add_unfiltered": 1, "splat": 2}                            # BLING_IMAGE_*
+
+
+class Filter(C.Structure):
+    """bling_filter (include/bling_scene.h)."""
+    _fields_ = [("kind", C.c_int32), ("width", C.c_float), ("height", C.c_float), ("table", C.c_float * 256)]
+
+
+class ImageDesc(C.Structure):
+    """bling_image_desc (include/bling_scene.h)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("filter", Filter)]
+
+
+class ImageStats(C.Structure):
+    """bling_image_stats (include/bling.h)."""
+    _fields_ = [("samples", C.c_uint64), ("dropped_spectrum", C.c_uint64), ("dropped_position", C.c_uint64),
+                ("tile_pairs", C.c_uint64), ("chunks", C.c_uint64), ("ms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class RenderConfig(C.Structure):
     _fields_ = [("renderer", C.c_int32), ("sampler", C.c_int32), ("nu", C.c_int32), ("nv", C.c_int32),
                 ("spp", C.c_int32), ("max_depth", C.c_int32), ("sample_depth", C.c_int32),
@@ -174,6 +197,16 @@ def host() -> C.CDLL:
         lib.bling_host_write_png_rgb8.restype = C.c_int
         lib.bling_host_write_hdr_rgbe.argtypes = [C.c_char_p, c_u8p, C.c_int, C.c_int]
         lib.bling_host_write_hdr_rgbe.restype = C.c_int
+        lib.bling_host_make_filter.argtypes = [C.c_int, c_f32p, C.c_int, C.POINTER(Filter)]
+        lib.bling_host_make_filter.restype = C.c_int
+        lib.bling_host_eval_filter.argtypes = [C.c_int, c_f32p, C.c_float, C.c_float]
+        lib.bling_host_eval_filter.restype = C.c_float
+        lib.bling_host_image_extent.argtypes = [C.POINTER(ImageDesc), C.POINTER(C.c_int32)]
+        lib.bling_host_image_extent.restype = None
+        lib.bling_host_image_add_samples.argtypes = [C.POINTER(ImageDesc), C.c_int, c_f32p, c_f32p, C.c_size_t, c_f32p]
+        lib.bling_host_image_add_samples.restype = C.c_int
+        lib.bling_host_rgb_to_spectrum_illum.argtypes = [c_f32p, c_f32p]
+        lib.bling_host_rgb_to_spectrum_illum.restype = None
         _host = lib
     return _host
 
@@ -182,7 +215,9 @@ HIP_SYMBOLS = ["bling_create", "bling_scene_upload", "bling_scene_validate", "bl
                "bling_trace", "bling_trace_device", "bling_sample_li", "bling_sample_li_vertices", "bling_pass_tile_layout",
                "bling_film_add_tiles", "bling_film_add_shards", "bling_sppm_pass", "bling_sppm_pixel_stats", "bling_sppm_reset",
                "bling_render", "bling_debug_stream_bytes", "bling_debug_scene_info", "bling_debug_mis_culled", "bling_debug_set_mis_cull", "bling_debug_set_pipeline", "bling_debug_pass_results", "bling_debug_compact", "bling_debug_sppm_hitpoints", "bling_debug_sppm_buckets",
-               "bling_film_develop", "bling_film_develop_device", "bling_light_pass", "bling_debug_light_records", "bling_mlt_pass", "bling_debug_mlt_records", "bling_debug_mlt_boot", "bling_debug_mlt_set_boot", "bling_light_pass_device", "bling_mlt_pass_device", "bling_debug_splat_merge", "bling_debug_set_splat_budget", "bling_debug_splat_times", "bling_sppm_pass_device", "bling_debug_sppm_records", "bling_debug_bidir_terms", "bling_destroy", "bling_last_error", "bling_version"]
+               "bling_film_develop", "bling_film_develop_device", "bling_light_pass", "bling_debug_light_records", "bling_mlt_pass", "bling_debug_mlt_records", "bling_debug_mlt_boot", "bling_debug_mlt_set_boot", "bling_light_pass_device", "bling_mlt_pass_device", "bling_debug_splat_merge", "bling_debug_set_splat_budget", "bling_debug_splat_times", "bling_sppm_pass_device", "bling_debug_sppm_records", "bling_debug_bidir_terms",
+               "bling_image_add_samples_device", "bling_image_add_samples", "bling_image_develop_device", "bling_debug_set_image_budget",
+               "bling_destroy", "bling_last_error", "bling_version"]
 
 
 class Progress(C.Structure):
@@ -290,6 +325,17 @@ def hip() -> C.CDLL:
             lib.bling_film_develop_device.restype = C.c_int
             lib.bling_film_develop.argtypes = [C.c_void_p, C.POINTER(DevelopParams), c_f32p, c_f32p, C.c_void_p]
             lib.bling_film_develop.restype = C.c_int
+        lib.bling_image_add_samples_device.argtypes = [C.c_void_p, C.POINTER(ImageDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                       C.c_void_p, C.POINTER(ImageStats)]
+        lib.bling_image_add_samples_device.restype = C.c_int
+        lib.bling_image_add_samples.argtypes = [C.c_void_p, C.POINTER(ImageDesc), C.c_int, c_f32p, c_f32p, C.c_size_t, c_f32p,
+                                                C.POINTER(ImageStats)]
+        lib.bling_image_add_samples.restype = C.c_int
+        lib.bling_image_develop_device.argtypes = [C.c_void_p, C.POINTER(ImageDesc), C.POINTER(DevelopParams), C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]
+        lib.bling_image_develop_device.restype = C.c_int
+        lib.bling_debug_set_image_budget.argtypes = [C.c_void_p, C.c_size_t]
+        lib.bling_debug_set_image_budget.restype = C.c_int
         lib.bling_debug_scene_info.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
         lib.bling_debug_scene_info.restype = C.c_int
         if hasattr(lib, "bling_debug_mis_culled"):    # older experiment builds lack it

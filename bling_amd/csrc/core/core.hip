@@ -933,23 +933,11 @@ int render_fanout(bling_ctx* c, const bling_pass_params* p, float* film_dev, bli
   return BLING_OK;
 }
 
-template <class F>
-int guarded(F f) {
-  try {
-    return f();
-  } catch (const HipError& e) {
-    g_err = e.what();
-    return BLING_EHIP;
-  } catch (const std::bad_alloc&) {
-    g_err = "out of memory";
-    return BLING_ENOMEM;
-  } catch (const std::exception& e) {
-    g_err = e.what();
-    return BLING_EINVAL;
-  }
-}
-
 }  // namespace
+
+namespace bcore {
+void set_last_error(const std::string& msg) { g_err = msg; }
+}  // namespace bcore
 
 extern "C" {
 

@@ -181,10 +181,42 @@ struct MergeState {
   }
 };
 
+// Image API state (image_ops.hip): per-sample results (X, Y, Z, valid) of one chunk, the per-tile counts,
+// segment starts, the scan's block sums and the (tile, sample) pair buffer, the drop / pair counters, the
+// host variant's staging buffers, and the pair budget (0: the default)
+struct ImageState {
+  DBuf<float4> res;
+  DBuf<uint32_t> cnt, start, sums, pairs;
+  DBuf<unsigned long long> ctr;
+  DBuf<float> xy, spectra, target;
+  size_t budget = 0;
+};
+
 }  // namespace bcore
 
 struct bling_ctx;
 namespace bcore {
+// core.hip: the thread's bling_last_error text, for entry points defined in other units
+void set_last_error(const std::string& msg);
+// runs an entry point's body: no C++ exception crosses the ABI, the error text is kept for bling_last_error
+template <class F>
+int guarded(F f) {
+  try {
+    return f();
+  } catch (const HipError& e) {
+    set_last_error(e.what());
+    return BLING_EHIP;
+  } catch (const std::bad_alloc&) {
+    set_last_error("out of memory");
+    return BLING_ENOMEM;
+  } catch (const std::exception& e) {
+    set_last_error(e.what());
+    return BLING_EINVAL;
+  }
+}
+// splat_merge.hip: start[0 .. n] = the exclusive prefix of cnt[0 .. n) (start[n] the total), enqueued on s;
+// sums holds (n + 1023) / 1024 + 1 words of scratch
+void sm_scan(hipStream_t s, const uint32_t* cnt, uint32_t n, uint32_t* sums, uint32_t* start);
 // splat_merge.hip: the record budget of this context's ordered passes; the ordered merge of n records
 // (layout SM_LAYOUT_*) into the device image img (W * H * 3), enqueued on the context's stream
 size_t splat_budget(bling_ctx* c);
@@ -195,6 +227,8 @@ size_t develop_pixel_bytes(int format);
 bool develop_clip(const bling_ctx* c, const int32_t* window, int* x0, int* x1, int* y0, int* y1);
 void develop_table(bling_ctx* c);
 void develop_launch(bling_ctx* c, const bling_develop_params* dp, const float* film, const float* splat, void* out);
+// the same for an image of w x h pixels that is not the uploaded scene's (bling_image_develop_device)
+void develop_launch(bling_ctx* c, const bling_develop_params* dp, int w, int h, const float* film, const float* splat, void* out);
 }  // namespace bcore
 
 // the context lives in the global namespace (include/bling.h declares `struct bling_ctx`)
@@ -319,6 +353,7 @@ struct bling_ctx {
   DBuf<const float4*> rank_bufs;   // the ordered merge's per-rank tile-image buffers (k_film_add_ordered)
   std::vector<std::unique_ptr<DBuf<float>>> stage;  // primary: landing buffer of peer j's tile images
   MergeState merge;                // the ordered splat merge (splat_merge.h)
+  ImageState image;                // the image API (image_ops.hip)
 
   ~bling_ctx() {
     peers.clear();                          // each peer frees its memory on its own device

@@ -89,10 +89,16 @@ size_t develop_pixel_bytes(int format) {
   return format == BLING_DEVELOP_RGB_F32 ? 12 : format == BLING_DEVELOP_RGB8 ? 3 : 4;
 }
 
-bool develop_clip(const bling_ctx* c, const int32_t* win, int* x0, int* x1, int* y0, int* y1) {
-  *x0 = std::max(win[0], 0); *x1 = std::min(win[1], c->S.width - 1);
-  *y0 = std::max(win[2], 0); *y1 = std::min(win[3], c->S.height - 1);
+namespace {
+bool clip_window(int w, int h, const int32_t* win, int* x0, int* x1, int* y0, int* y1) {
+  *x0 = std::max(win[0], 0); *x1 = std::min(win[1], w - 1);
+  *y0 = std::max(win[2], 0); *y1 = std::min(win[3], h - 1);
   return *x0 <= *x1 && *y0 <= *y1;
+}
+}  // namespace
+
+bool develop_clip(const bling_ctx* c, const int32_t* win, int* x0, int* x1, int* y0, int* y1) {
+  return clip_window(c->S.width, c->S.height, win, x0, x1, y0, y1);
 }
 
 void develop_table(bling_ctx* c) {
@@ -104,13 +110,17 @@ void develop_table(bling_ctx* c) {
 
 // one launch on the context's stream; the caller synchronises
 void develop_launch(bling_ctx* c, const bling_develop_params* dp, const float* film, const float* splat, void* out) {
+  develop_launch(c, dp, c->S.width, c->S.height, film, splat, out);
+}
+
+void develop_launch(bling_ctx* c, const bling_develop_params* dp, int w, int h, const float* film, const float* splat, void* out) {
   int x0, x1, y0, y1;
-  if (!develop_clip(c, dp->window, &x0, &x1, &y0, &y1)) return;   // a window outside the image writes nothing
+  if (!clip_window(w, h, dp->window, &x0, &x1, &y0, &y1)) return;   // a window outside the image writes nothing
   const int ww = x1 - x0 + 1;
   const uint64_t n64 = (uint64_t)ww * (uint64_t)(y1 - y0 + 1);
   if (n64 > 0xFFFFFF00ull) throw std::invalid_argument("develop: window too large");
   const uint32_t n = (uint32_t)n64, blocks = (n + 255u) / 256u;
-  const int w = c->S.width, a4 = ((uintptr_t)out & 3u) == 0;
+  const int a4 = ((uintptr_t)out & 3u) == 0;
   const float sw = dp->splat_weight, *tab = c->gamma_tab.p;
   hipStream_t s = c->stream;
   switch (dp->format) {

@@ -11,6 +11,7 @@
 //   k_sm_long      one block per listed segment: all-ascending bitonic network over (key, position) in LDS up
 //                  to SM_LDS_RECORDS records, over keys and values in place in global memory beyond; then
 //                  the values are staged 256 at a time and three lanes (X, Y, Z) add them one by one
+// sm_bitonic, that network, is defined here: the image API's tile segments (image_ops.hip) are sorted by it too.
 #pragma once
 #include <cstdint>
 
@@ -32,6 +33,33 @@ DEV void sm_write_rec(uint4* __restrict__ rec, size_t slot, uint32_t pixel, unsi
                       uint32_t tag = 0u) {
   rec[2 * slot] = make_uint4(pixel, tag, (uint32_t)key, (uint32_t)(key >> 32));
   rec[2 * slot + 1] = make_uint4(__float_as_uint(x), __float_as_uint(y), __float_as_uint(z), 0u);
+}
+
+// The all-ascending bitonic network over len elements as if padded with +inf to a power of two: a
+// comparator whose upper element is padding does nothing, and every comparator puts the larger element
+// at the higher index, so padding never moves.  X::cswap(lo, hi) orders one pair.
+template <class X>
+DEV void sm_bitonic(X& x, uint32_t len) {
+  uint32_t P = 1;
+  while (P < len) P <<= 1;
+  const uint32_t half = P >> 1;
+  for (uint32_t k = 2; k <= P; k <<= 1) {
+    const uint32_t hk = k >> 1;
+    for (uint32_t i = threadIdx.x; i < half; i += blockDim.x) {        // the two sorted halves, mirrored
+      const uint32_t blk = i / hk, off = i - blk * hk;
+      const uint32_t lo = blk * k + off, hi = blk * k + (k - 1u - off);
+      if (hi < len) x.cswap(lo, hi);
+    }
+    __syncthreads();
+    for (uint32_t j = k >> 2; j > 0; j >>= 1) {                        // half-cleaners
+      for (uint32_t i = threadIdx.x; i < half; i += blockDim.x) {
+        const uint32_t blk = i / j, off = i - blk * j;
+        const uint32_t lo = blk * 2u * j + off, hi = lo + j;
+        if (hi < len) x.cswap(lo, hi);
+      }
+      __syncthreads();
+    }
+  }
 }
 
 }  // namespace bd

@@ -152,33 +152,6 @@ __global__ __launch_bounds__(256) void k_sm_short(const uint32_t* __restrict__ s
   }
 }
 
-// The all-ascending bitonic network over len elements as if padded with +inf to a power of two: a
-// comparator whose upper element is padding does nothing, and every comparator puts the larger element
-// at the higher index, so padding never moves.  X::cswap(lo, hi) orders one pair.
-template <class X>
-DEV void sm_bitonic(X& x, uint32_t len) {
-  uint32_t P = 1;
-  while (P < len) P <<= 1;
-  const uint32_t half = P >> 1;
-  for (uint32_t k = 2; k <= P; k <<= 1) {
-    const uint32_t hk = k >> 1;
-    for (uint32_t i = threadIdx.x; i < half; i += blockDim.x) {        // the two sorted halves, mirrored
-      const uint32_t blk = i / hk, off = i - blk * hk;
-      const uint32_t lo = blk * k + off, hi = blk * k + (k - 1u - off);
-      if (hi < len) x.cswap(lo, hi);
-    }
-    __syncthreads();
-    for (uint32_t j = k >> 2; j > 0; j >>= 1) {                        // half-cleaners
-      for (uint32_t i = threadIdx.x; i < half; i += blockDim.x) {
-        const uint32_t blk = i / j, off = i - blk * j;
-        const uint32_t lo = blk * 2u * j + off, hi = lo + j;
-        if (hi < len) x.cswap(lo, hi);
-      }
-      __syncthreads();
-    }
-  }
-}
-
 struct SmLds {          // (key, position) pairs in LDS
   unsigned long long* k;
   uint32_t* j;
@@ -259,6 +232,13 @@ size_t splat_budget(bling_ctx* c) {
   return c->merge.default_budget;
 }
 
+void sm_scan(hipStream_t s, const uint32_t* cnt, uint32_t n, uint32_t* sums, uint32_t* start) {
+  const uint32_t nb = (n + kScanChunk - 1) / kScanChunk;
+  k_sm_sums<<<nb, 256, 0, s>>>(cnt, n, sums);
+  k_sm_scan_sums<<<1, 256, 0, s>>>(sums, nb);
+  k_sm_starts<<<nb, 256, 0, s>>>(cnt, n, sums, nb, start);
+}
+
 void splat_merge(bling_ctx* c, const uint4* recs, size_t n, int layout, float* img) {
   if (n == 0) return;
   if (n > 0x7FFFFFFFull) throw std::invalid_argument("splat merge: more than 2^31 - 1 records");
@@ -271,9 +251,7 @@ void splat_merge(bling_ctx* c, const uint4* recs, size_t n, int layout, float* i
   HIPCHK(hipMemsetAsync(M.cnt.p, 0, (size_t)npix * sizeof(uint32_t), s));
   HIPCHK(hipMemsetAsync(M.longs.p, 0, sizeof(uint32_t), s));
   k_sm_count<<<stride_grid(n), 256, 0, s>>>(recs, n, layout, W, npix, M.cnt.p);
-  k_sm_sums<<<nb, 256, 0, s>>>(M.cnt.p, npix, M.sums.p);
-  k_sm_scan_sums<<<1, 256, 0, s>>>(M.sums.p, nb);
-  k_sm_starts<<<nb, 256, 0, s>>>(M.cnt.p, npix, M.sums.p, nb, M.start.p);
+  sm_scan(s, M.cnt.p, npix, M.sums.p, M.start.p);
   k_sm_scatter<<<stride_grid(n), 256, 0, s>>>(recs, n, layout, W, npix, M.start.p, M.cnt.p, M.key.p, M.val.p);
   k_sm_short<<<stride_grid(npix), 256, 0, s>>>(M.start.p, npix, M.key.p, M.val.p, img, M.longs.p);
   k_sm_long<<<(unsigned)std::min<size_t>(1024, std::max<size_t>(1, n / (SM_SHORT + 1))), 256, 0, s>>>(M.start.p, M.key.p, M.val.p, img,

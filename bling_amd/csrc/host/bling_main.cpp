@@ -11,12 +11,20 @@
 // --film ordered (sampler scenes; the environment's BLING_FILM_ORDERED=1 means the same) forms every pass's film in
 // the reference's order without float atomics (BLING_PASS_ORDERED_FILM): the same files on every run.  The splat
 // renderers refuse it: their switch is --splat.
+//   bling --image-filters [--out DIR] [--size WxH] [--develop host|device] [--device D]
+// reproduces the reference's live command line (main = imageFilters, src/cmdline/Examples.hs:10-58) and is the whole
+// run: for box, gauss 3 3 2, mitchell 3 3 1/3 1/3, sinc 3 3 3 and triangle 3 3 it writes DIR/filter-show-<name>.png
+// (64 x 64, box film, red or green by the sign of evalFilter) and DIR/filter-test-<name>.png (480 x 270 unless --size
+// says otherwise, 25 offsets a pixel over the sample extent, |sin (150 r^2)| grey through rgbToSpectrumIllum).  The
+// samples are made on the host in row chunks and added on the device in order (bling_image_add_samples_device).
 // With --develop device, or --splat ordered, such a scene's splat image (and an SPPM scene's film) lives on
 // the device for the whole run (bling_light_pass_device / bling_mlt_pass_device / bling_sppm_pass_device);
 // --develop device then develops it there (bling_film_develop_device) and only the developed pixels come back.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -100,13 +108,166 @@ int write_pass(bling_ctx* ctx, bool on_device, const std::string& name, const fl
   }
   return 0;
 }
+
+// execImageT of one of imageFilters' two sample generators over an image on the device, then writePng.
+struct FilterImage {
+  bling_ctx* ctx;
+  bool dev_develop;
+  bling_image_desc desc{};
+  void *film = nullptr, *xy = nullptr, *spectra = nullptr, *out = nullptr;
+  size_t cap = 0;                               // samples xy and spectra hold
+  std::vector<float> hxy, hsp;
+  bling_image_stats total{};
+  ~FilterImage() { (void)hipFree(film); (void)hipFree(xy); (void)hipFree(spectra); (void)hipFree(out); }
+  bool start(const bling_filter& f, int w, int h) {
+    desc.width = w; desc.height = h; desc.filter = f;
+    total = bling_image_stats{};
+    (void)hipFree(film); (void)hipFree(out);
+    film = out = nullptr;
+    const size_t px = (size_t)w * h;
+    return hipMalloc(&film, px * 16) == hipSuccess && hipMemset(film, 0, px * 16) == hipSuccess && hipMalloc(&out, px * 3) == hipSuccess;
+  }
+  void sample(float x, float y, const float rgb[3]) {
+    hxy.push_back(x); hxy.push_back(y);
+    hsp.resize(hsp.size() + 16);
+    bling_host_rgb_to_spectrum_illum(rgb, hsp.data() + hsp.size() - 16);
+  }
+  // addSample' of the samples gathered so far, in order
+  bool flush() {
+    const size_t n = hxy.size() / 2;
+    if (n == 0) return true;
+    if (n > cap) {
+      (void)hipFree(xy); (void)hipFree(spectra);
+      xy = spectra = nullptr;
+      if (hipMalloc(&xy, n * 8) != hipSuccess || hipMalloc(&spectra, n * 64) != hipSuccess) { cap = 0; return false; }
+      cap = n;
+    }
+    if (hipMemcpy(xy, hxy.data(), n * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(spectra, hsp.data(), n * 64, hipMemcpyHostToDevice) != hipSuccess)
+      return false;
+    bling_image_stats st;
+    if (bling_image_add_samples_device(ctx, &desc, BLING_IMAGE_ADD, xy, spectra, n, film, &st) != 0) {
+      std::fprintf(stderr, "%s\n", bling_last_error());
+      return false;
+    }
+    total.samples += st.samples; total.tile_pairs += st.tile_pairs; total.chunks += st.chunks; total.ms += st.ms;
+    total.dropped_spectrum += st.dropped_spectrum; total.dropped_position += st.dropped_position;
+    hxy.clear(); hsp.clear();
+    return true;
+  }
+  bool write(const std::string& path) {
+    const int w = desc.width, h = desc.height;
+    const size_t px = (size_t)w * h;
+    int rc;
+    if (dev_develop) {
+      std::vector<unsigned char> px8(px * 3);
+      bling_develop_params dp{BLING_DEVELOP_RGB8, 0.f, {0, w - 1, 0, h - 1}};
+      if (bling_image_develop_device(ctx, &desc, &dp, film, nullptr, out) != 0) { std::fprintf(stderr, "%s\n", bling_last_error()); return false; }
+      if (hipMemcpy(px8.data(), out, px * 3, hipMemcpyDeviceToHost) != hipSuccess) return false;
+      rc = bling_host_write_png_rgb8(path.c_str(), px8.data(), w, h);
+    } else {
+      std::vector<float> host(px * 4);
+      if (hipMemcpy(host.data(), film, px * 16, hipMemcpyDeviceToHost) != hipSuccess) return false;
+      rc = bling_host_write_png(path.c_str(), host.data(), w, h);
+    }
+    if (rc != 0) std::fprintf(stderr, "%s\n", bling_host_last_error());
+    return rc == 0;
+  }
+};
+
+int image_filters(int argc, char** argv) {
+  const char* dir = ".";
+  int width = 480, height = 270, device = 0;
+  bool dev_develop = false;
+  for (int i = 2; i + 1 < argc; i += 2) {
+    if (!std::strcmp(argv[i], "--out")) dir = argv[i + 1];
+    else if (!std::strcmp(argv[i], "--device")) device = std::atoi(argv[i + 1]);
+    else if (!std::strcmp(argv[i], "--size")) {
+      if (std::sscanf(argv[i + 1], "%dx%d", &width, &height) != 2 || width < 1 || height < 1) {
+        std::fprintf(stderr, "--size takes WxH, not %s\n", argv[i + 1]);
+        return 2;
+      }
+    } else if (!std::strcmp(argv[i], "--develop")) {
+      if (std::strcmp(argv[i + 1], "host") && std::strcmp(argv[i + 1], "device")) {
+        std::fprintf(stderr, "--develop takes host or device, not %s\n", argv[i + 1]);
+        return 2;
+      }
+      dev_develop = !std::strcmp(argv[i + 1], "device");
+    } else {
+      std::fprintf(stderr, "--image-filters: unknown option %s\n", argv[i]);
+      return 2;
+    }
+  }
+  struct Flt { const char* name; int kind; int n; float p[4]; };
+  const Flt flts[] = {{"box", BLING_FILTER_BOX, 0, {}},
+                      {"gauss", BLING_FILTER_GAUSS, 3, {3.f, 3.f, 2.f}},
+                      {"mitchell", BLING_FILTER_MITCHELL, 4, {3.f, 3.f, 1.f / 3.f, 1.f / 3.f}},
+                      {"sinc", BLING_FILTER_SINC, 3, {3.f, 3.f, 3.f}},
+                      {"triangle", BLING_FILTER_TRIANGLE, 2, {3.f, 3.f}}};
+  bling_ctx* ctx = nullptr;
+  if (bling_create(&device, 1, &ctx) != 0 || hipSetDevice(device) != hipSuccess) { std::fprintf(stderr, "%s\n", bling_last_error()); return 1; }
+  int rc = 0;
+  {
+    FilterImage img{ctx, dev_develop};
+    bling_filter box;
+    bling_host_make_filter(BLING_FILTER_BOX, nullptr, 0, &box);
+    constexpr int kShow = 64, kRows = 16;       // showSize; sample-extent rows per device call
+    const float offs[5] = {0.f, 0.2f, 0.4f, 0.6f, 0.8f};
+    for (const Flt& f : flts) {
+      std::printf("%s\n", f.name);
+      bling_filter flt;
+      if (bling_host_make_filter(f.kind, f.p, f.n, &flt) != 0) { std::fprintf(stderr, "%s\n", bling_host_last_error()); rc = 1; break; }
+      int32_t e[4];
+      // fltShow: the filter's own shape, through a box film
+      if (!img.start(box, kShow, kShow)) { std::fprintf(stderr, "device film: allocation failed\n"); rc = 1; break; }
+      bling_host_image_extent(&img.desc, e);
+      bool ok = true;
+      for (int py = e[2]; py <= e[3] && ok; ++py) {
+        for (int px = e[0]; px <= e[1]; ++px) {
+          const float x = (float)px, y = (float)py;
+          const float xs = (x / (float)kShow - 0.5f) * 4.f, ys = (y / (float)kShow - 0.5f) * 4.f;
+          const float d = bling_host_eval_filter(f.kind, f.p, xs, ys);
+          const float c[3] = {d > 0.f ? d : 0.f, d > 0.f ? 0.f : -d, 0.f};
+          img.sample(x, y, c);
+        }
+        if ((py - e[2]) % kRows == kRows - 1 || py == e[3]) ok = img.flush();
+      }
+      const std::string base = std::string(dir) + "/filter-";
+      if (!ok || !img.write(base + "show-" + f.name + ".png")) { rc = 1; break; }
+      // fltTest: a zone plate through the filter
+      if (!img.start(flt, width, height)) { std::fprintf(stderr, "device film: allocation failed\n"); rc = 1; break; }
+      bling_host_image_extent(&img.desc, e);
+      const float sz = (float)std::min(width, height);
+      for (int py = e[2]; py <= e[3] && ok; ++py) {
+        for (int px = e[0]; px <= e[1]; ++px)
+          for (float sx : offs)
+            for (float sy : offs) {
+              const float x = (float)px + sx, y = (float)py + sy;
+              const float dx = x / sz - 0.5f, dy = 1.f - y / sz;
+              const float d = std::fabs(std::sin(150.f * (dx * dx + dy * dy)));
+              const float c[3] = {d, d, d};
+              img.sample(x, y, c);
+            }
+        if ((py - e[2]) % kRows == kRows - 1 || py == e[3]) ok = img.flush();
+      }
+      if (!ok || !img.write(base + "test-" + f.name + ".png")) { rc = 1; break; }
+      std::printf("   filter-test-%s: %llu samples, %llu tile pairs, %llu chunks, %.2f ms on the device\n", f.name,
+                  (unsigned long long)img.total.samples, (unsigned long long)img.total.tile_pairs, (unsigned long long)img.total.chunks,
+                  img.total.ms);
+    }
+  }
+  bling_destroy(ctx);
+  return rc;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    std::fprintf(stderr, "usage: %s scene.bling [--overrides S] [--passes N] [--out prefix] [--device D] [--develop host|device] [--splat atomic|ordered] [--film atomic|ordered]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s scene.bling [--overrides S] [--passes N] [--out prefix] [--device D] [--develop host|device] [--splat atomic|ordered] [--film atomic|ordered]\n"
+                         "       %s --image-filters [--out DIR] [--size WxH] [--develop host|device] [--device D]\n", argv[0], argv[0]);
     return 2;
   }
+  if (!std::strcmp(argv[1], "--image-filters")) return image_filters(argc, argv);
   const char* scene = argv[1];
   const char* ov = nullptr;
   const char* out = "pass";

@@ -26,6 +26,7 @@
 #include "../common/sky_model.h"
 #include "../common/cr_math.h"
 #include "../common/gamma_table.h"
+#include "../common/image_sample.h"
 #include "hmath.h"
 #include "image_io.h"
 
@@ -1499,6 +1500,80 @@ float bling_host_sppm_splat_weight(const bling_render_config* cfg, int pass, int
   const int sn = std::max(1, (int)std::ceil(std::sqrt((float)cfg->sppm_photons / (float)threads)));
   if (sn_out) *sn_out = sn;
   return 1.f / (float)((long long)threads * pass * sn * sn);
+}
+
+namespace {
+// the parameters build_filter / eval_filter take, from the n a caller gives (pFilter's: box none, gauss w h
+// alpha, sinc w h tau, mitchell w h b c, triangle w h); false for a wrong count or an unknown kind
+bool filter_params(int kind, const float* params, int n, float p[5]) {
+  static const int want[5] = {0, 3, 3, 4, 2};
+  if (kind < BLING_FILTER_BOX || kind > BLING_FILTER_TRIANGLE || n != want[kind] || (n && !params)) return false;
+  for (int i = 0; i < 5; ++i) p[i] = i < n ? params[i] : 0.f;
+  if (kind == BLING_FILTER_GAUSS) { p[3] = std::exp(-p[2] * p[0] * p[0]); p[4] = std::exp(-p[2] * p[1] * p[1]); }   // mkGaussFilter
+  return true;
+}
+}  // namespace
+
+int bling_host_make_filter(int kind, const float* params, int n, bling_filter* out) {
+  float p[5];
+  if (!out || !filter_params(kind, params, n, p)) { g_err = "make_filter: unknown kind or wrong parameter count"; return -1; }
+  build_filter(*out, kind, p);
+  return 0;
+}
+
+float bling_host_eval_filter(int kind, const float* params, float x, float y) {
+  static const int want[5] = {0, 3, 3, 4, 2};
+  float p[5];
+  if (kind < BLING_FILTER_BOX || kind > BLING_FILTER_TRIANGLE || !filter_params(kind, params, want[kind], p)) return 0.f;
+  return eval_filter(kind, p, x, y);
+}
+
+void bling_host_image_extent(const bling_image_desc* d, int32_t out4[4]) {
+  // sampleExtent of an image at offset (0, 0) (Image.hs:162-168)
+  const float fw = d->filter.width, fh = d->filter.height;
+  out4[0] = (int32_t)std::floor(0.5f - fw);
+  out4[1] = (int32_t)std::floor(0.5f + (float)d->width + fw);
+  out4[2] = (int32_t)std::floor(0.5f - fh);
+  out4[3] = (int32_t)std::floor(0.5f + (float)d->height + fh);
+}
+
+void bling_host_rgb_to_spectrum_illum(const float rgb[3], float out16[16]) {
+  const Spec s = rgb_to_spectrum(BLING_RGB_ILLUM_BANDS, rgb[0], rgb[1], rgb[2]);
+  std::copy(s.begin(), s.end(), out16);
+}
+
+int bling_host_image_add_samples(const bling_image_desc* d, int op, const float* xy, const float* spectra, size_t n, float* target) {
+  using namespace bimgs;
+  if (!d || !target || (n && (!xy || !spectra))) { g_err = "image: null argument"; return -1; }
+  if (op != OP_ADD && op != OP_UNFILTERED && op != OP_SPLAT) { g_err = "image: unknown op"; return -1; }
+  const int w = d->width, h = d->height;
+  const float fw = d->filter.width, fh = d->filter.height;
+  if (w < 1 || h < 1 || !(finite_f(fw) && finite_f(fh) && fw > 0.f && fh > 0.f)) { g_err = "image: bad size or filter size"; return -1; }
+  const float ifw = 1.f / fw, ifh = 1.f / fw;                          // trap T12
+  for (size_t i = 0; i < n; ++i) {
+    const float sx = xy[2 * i], sy = xy[2 * i + 1], *b = spectra + 16 * i;
+    if (!position_ok(sx, sy) || !spectrum_ok(b)) continue;
+    int x0, x1, y0, y1;
+    if (!sample_rect(op, sx, sy, fw, fh, w, h, &x0, &x1, &y0, &y1)) continue;
+    float X, Y, Z;
+    to_xyz(b, &X, &Y, &Z);
+    if (op == OP_SPLAT) {
+      float* o = target + 3 * ((size_t)y0 * w + x0);
+      o[0] = o[0] + X; o[1] = o[1] + Y; o[2] = o[2] + Z;
+    } else if (op == OP_UNFILTERED) {
+      float* o = target + 4 * ((size_t)y0 * w + x0);
+      o[0] = o[0] + 1.f; o[1] = o[1] + X; o[2] = o[2] + Y; o[3] = o[3] + Z;
+    } else {
+      const float dx = sx - 0.5f, dy = sy - 0.5f;
+      for (int y = y0; y <= y1; ++y)
+        for (int x = x0; x <= x1; ++x) {
+          const float fltw = d->filter.table[table_index(y, dy, ifh) * 16 + table_index(x, dx, ifw)];
+          float* o = target + 4 * ((size_t)y * w + x);
+          o[0] = o[0] + fltw; o[1] = o[1] + X * fltw; o[2] = o[2] + Y * fltw; o[3] = o[3] + Z * fltw;
+        }
+    }
+  }
+  return 0;
 }
 
 const char* bling_host_summary(const bling_host_scene* s) { return s ? s->b.summary.c_str() : ""; }

@@ -541,6 +541,60 @@ int bling_debug_set_splat_budget(bling_ctx* ctx, size_t max_records);
  * its merges (their sum is the pass's ms_total). */
 int bling_debug_splat_times(bling_ctx* ctx, double* ms_kernel, double* ms_merge);
 
+/* ---- the image API on the device: caller samples onto a film, in order ----
+ * Replaces: the image monad of Image.hs -- addSample', addUnfilteredSample', splatSample and execImageT
+ * (Image.hs:201-299, 333-370) -- for samples the CALLER computed: what the reference's live command line
+ * does (imageFilters, src/cmdline/Examples.hs) and what a host-side Renderer instance uses to put its own
+ * samples on a device film.  These calls need NO uploaded scene and leave an uploaded one untouched (SPPM,
+ * light tracer and Metropolis state included); width, height and filter come from the desc.  They run on
+ * device_ids[0], on the context's stream, and return after completion.
+ *   xy: 2 floats per sample (imageX, imageY); spectra: 16 floats per sample; n samples.
+ *   target: width*height*4 floats (W, X, Y, Z) for BLING_IMAGE_ADD and BLING_IMAGE_ADD_UNFILTERED,
+ *   width*height*3 floats (XYZ) for BLING_IMAGE_SPLAT; ACCUMULATED into.
+ * The order promise: the target after the call is, bit for bit in binary32, what the reference's one thread
+ * makes of it by applying the op to samples 0 .. n-1 in that order, the incoming target value being the first
+ * operand: per pixel and channel a = a + w for W and a = a + (v * w) for X, Y, Z with the product rounded
+ * first (a = a + 1, a = a + v for the two unfiltered ops), the contributing samples in ascending index.
+ * XYZ comes from the 16 bands as the film kernels form it (three sequential binary32 sums divided by
+ * BLING_CIE_Y_SUM); trap T12 (ifh = 1 / fw) is kept.  Hence two calls with lists A then B give the same bits
+ * as one call with A followed by B, and the same list gives the same bytes on every run.  No float atomic is
+ * used anywhere: integer atomics count and claim slots, and nothing depends on their order.
+ * The drop rules, the same in bling_host_image_add_samples (bling_host.h):
+ *   - a sample whose x or y is NaN, infinite or exceeds 2^20 in magnitude is dropped and counted in
+ *     dropped_position (the reference's ceiling / floor of such a position are meaningless);
+ *   - of the others, a sample with a NaN or infinite band is dropped and counted in dropped_spectrum
+ *     (Image.hs:204-208, 225-229, 253-256), whether or not it would have landed inside the image;
+ *   - a sample that reaches no pixel of the image adds nothing and is counted nowhere.
+ * The (16 x 16 destination tile, sample) pairs go through a pair buffer of at most 64 MiB (4 bytes a pair;
+ * bling_debug_set_image_budget sets another bound, in pairs): a longer list is cut into chunks of consecutive
+ * samples applied one after another, which the composition rule makes legal; stats->chunks is their number
+ * and stats->tile_pairs the pairs written.  stats (may be NULL): ms is the device time of the call (HIP events).
+ * Errors: BLING_EINVAL for a NULL ctx / desc / xy / spectra / target (xy and spectra may be NULL when n == 0),
+ * an unknown op, width or height < 1 (or width * height > 2^28), a filter width or height that is NaN,
+ * infinite or <= 0, or a target that overlaps xy or spectra.  n == 0 leaves the target as it was.
+ * bling_image_add_samples_device: xy, spectra and target are device buffers on device_ids[0] (e.g. torch
+ *   tensors' data_ptr()); nothing crosses to the host.
+ * bling_image_add_samples: the three are host buffers, staged through device buffers the context owns.
+ * bling_image_develop_device: bling_film_develop_device with the width and height of the desc instead of an
+ *   uploaded scene's: the same three formats, window rule and overlap check; no scene needed. */
+/* bling_image_desc and the BLING_IMAGE_* ops: bling_scene.h, shared with the host library */
+typedef struct bling_image_stats {
+    uint64_t samples;          /* n                                                              */
+    uint64_t dropped_spectrum; /* samples dropped for a NaN / infinite band                      */
+    uint64_t dropped_position; /* samples dropped for a non-finite or huge position              */
+    uint64_t tile_pairs;       /* (destination tile, sample) pairs written                       */
+    uint64_t chunks;           /* chunks the list was cut into                                   */
+    double   ms;               /* device time of the call (HIP events)                           */
+} bling_image_stats;
+int bling_image_add_samples_device(bling_ctx* ctx, const bling_image_desc* desc, int op, const void* xy_dev,
+                                   const void* spectra_dev, size_t n, void* target_dev, bling_image_stats* stats);
+int bling_image_add_samples(bling_ctx* ctx, const bling_image_desc* desc, int op, const float* xy, const float* spectra,
+                            size_t n, float* target_host, bling_image_stats* stats);
+int bling_image_develop_device(bling_ctx* ctx, const bling_image_desc* desc, const bling_develop_params* p,
+                               const void* film_dev, const void* splat_dev, void* out_dev);
+/* Test hook: the pair budget of this context's image calls, in pairs; 0 restores the default (64 MiB). */
+int bling_debug_set_image_budget(bling_ctx* ctx, size_t max_tile_pairs);
+
 /* Diagnostics (no reference counterpart): the path-state bytes the shading kernel k_shade moved in
  * the context's last bling_render_pass*, per stream and direction -- out[2 k] read, out[2 k + 1]
  * written, stream k in the order BLING_STREAM_NAMES lists -- counted where the algorithm needs

@@ -10,6 +10,7 @@
 #ifndef BLING_HOST_H
 #define BLING_HOST_H
 
+#include <stddef.h>
 #include "bling_scene.h"
 
 #ifdef __cplusplus
@@ -89,6 +90,27 @@ void bling_host_gamma_thresholds(float* out255);
  * the same pixels give the same file. */
 int bling_host_write_png_rgb8(const char* path, const unsigned char* rgb8, int w, int h);
 int bling_host_write_hdr_rgbe(const char* path, const unsigned char* rgbe, int w, int h);
+
+/* ---- the host side of the image API (bling_image_*, bling.h) ----
+ * bling_host_make_filter: the bling_filter (size and 16 x 16 table, mkTableFilter) of a pixel filter given as
+ * the `filter` line of a scene file gives it: kind BLING_FILTER_* and its n parameters -- box none, gauss
+ * w h alpha, sinc w h tau, mitchell w h B C, triangle w h.  0, or -1 for an unknown kind or a wrong n.
+ * bling_host_eval_filter: evalFilter (Filter.hs:68-96) of that filter at (x, y); 0 for an unknown kind. */
+int   bling_host_make_filter(int kind, const float* params, int n, bling_filter* out);
+float bling_host_eval_filter(int kind, const float* params, float x, float y);
+/* sampleExtent (Image.hs:162-168) of the image: out4 = x0, x1, y0, y1, inclusive. */
+void  bling_host_image_extent(const bling_image_desc* desc, int32_t out4[4]);
+/* The sequential binary32 restatement of addSample, addUnfilteredSample and splatSample (Image.hs:201-299):
+ * op BLING_IMAGE_* applied to samples 0 .. n-1 in that order, accumulated into target (width*height*4 floats,
+ * or *3 for BLING_IMAGE_SPLAT).  xy: 2 floats a sample, spectra: 16.  Compiled without multiply-add
+ * contraction, as the oracle is; bling_image_add_samples[_device] gives the same bits.  The drop rules are
+ * those of bling.h: a sample whose x or y is NaN, infinite or beyond 2^20 in magnitude is dropped, and so is
+ * one with a NaN or infinite band.  0, or -1 for a NULL argument, an unknown op, width or height < 1, or a
+ * filter size that is not finite and positive. */
+int   bling_host_image_add_samples(const bling_image_desc* desc, int op, const float* xy, const float* spectra, size_t n,
+                                   float* target);
+/* rgbToSpectrumIllum (Spectrum.hs:146-159 over the illuminant bases), as the loader applies it to image maps. */
+void  bling_host_rgb_to_spectrum_illum(const float rgb[3], float out16[16]);
 
 #ifdef __cplusplus
 }

@@ -257,6 +257,15 @@ typedef struct bling_filter {
     float   table[256];        /* mkTableFilter (Image.hs:48-61)                              */
 } bling_filter;
 
+/* ---- an image of the image API (mkImage, Image.hs:137-144): bling_image_* (bling.h), bling_host_image_* ---- */
+typedef struct bling_image_desc {
+    int32_t      width, height;
+    bling_filter filter;       /* bling_host_make_filter (bling_host.h) builds one          */
+} bling_image_desc;
+#define BLING_IMAGE_ADD            0   /* addSample            (Image.hs:250-299) -> film, 4 floats a pixel  */
+#define BLING_IMAGE_ADD_UNFILTERED 1   /* addUnfilteredSample  (Image.hs:223-246) -> film                     */
+#define BLING_IMAGE_SPLAT          2   /* splatSample          (Image.hs:201-221) -> splat image, 3 floats    */
+
 /* ---- renderer configuration (IO/RendererParser.hs, IO/IntegratorParser.hs) ---- */
 enum bling_sampler_kind { BLING_SAMPLER_STRATIFIED = 0, BLING_SAMPLER_RANDOM = 1 };
 enum bling_renderer_kind {
