@@ -54,6 +54,16 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ImageWindow(C.Structure):
+    """bling_image_window (include/bling_scene.h): a SampleWindow, ends inclusive."""
+    _fields_ = [("x0", C.c_int32), ("x1", C.c_int32), ("y0", C.c_int32), ("y1", C.c_int32)]
+
+
+class ImageTile(C.Structure):
+    """bling_image_tile (include/bling_scene.h): mkImageTile's offset and size, and the tile's sampleExtent."""
+    _fields_ = [("px", C.c_int32), ("py", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("extent", C.c_int32 * 4)]
+
+
 class SppmStats(C.Structure):
     """bling_sppm_stats (include/bling.h)."""
     _fields_ = [("hitpoints", C.c_uint64), ("photons", C.c_uint64), ("photon_rays", C.c_uint64),
@@ -139,7 +149,7 @@ class ImageDesc(C.Structure):
 
 
 class ImageStats(C.Structure):
-    """bling_image_stats (include/bling.h)."""
+    """bling_image_stats (include/bling_scene.h)."""
     _fields_ = [("samples", C.c_uint64), ("dropped_spectrum", C.c_uint64), ("dropped_position", C.c_uint64),
                 ("tile_pairs", C.c_uint64), ("chunks", C.c_uint64), ("ms", C.c_double)]
 
@@ -205,6 +215,13 @@ def host() -> C.CDLL:
         lib.bling_host_image_extent.restype = None
         lib.bling_host_image_add_samples.argtypes = [C.POINTER(ImageDesc), C.c_int, c_f32p, c_f32p, C.c_size_t, c_f32p]
         lib.bling_host_image_add_samples.restype = C.c_int
+        lib.bling_host_image_tile.argtypes = [C.POINTER(ImageDesc), C.POINTER(ImageWindow), C.POINTER(ImageTile)]
+        lib.bling_host_image_tile.restype = C.c_int
+        lib.bling_host_image_add_windowed.argtypes = [C.POINTER(ImageDesc), C.c_int, C.POINTER(ImageWindow), C.POINTER(C.c_uint64),
+                                                      C.c_size_t, c_f32p, c_f32p, C.c_size_t, c_f32p, c_f32p, C.POINTER(ImageStats)]
+        lib.bling_host_image_add_windowed.restype = C.c_int
+        lib.bling_host_image_scale_splats.argtypes = [C.POINTER(ImageDesc), c_f32p, c_f32p, C.c_float]
+        lib.bling_host_image_scale_splats.restype = C.c_int
         lib.bling_host_rgb_to_spectrum_illum.argtypes = [c_f32p, c_f32p]
         lib.bling_host_rgb_to_spectrum_illum.restype = None
         _host = lib
@@ -217,6 +234,7 @@ HIP_SYMBOLS = ["bling_create", "bling_scene_upload", "bling_scene_validate", "bl
                "bling_render", "bling_debug_stream_bytes", "bling_debug_scene_info", "bling_debug_mis_culled", "bling_debug_set_mis_cull", "bling_debug_set_pipeline", "bling_debug_pass_results", "bling_debug_compact", "bling_debug_sppm_hitpoints", "bling_debug_sppm_buckets",
                "bling_film_develop", "bling_film_develop_device", "bling_light_pass", "bling_debug_light_records", "bling_mlt_pass", "bling_debug_mlt_records", "bling_debug_mlt_boot", "bling_debug_mlt_set_boot", "bling_light_pass_device", "bling_mlt_pass_device", "bling_debug_splat_merge", "bling_debug_set_splat_budget", "bling_debug_splat_times", "bling_sppm_pass_device", "bling_debug_sppm_records", "bling_debug_bidir_terms",
                "bling_image_add_samples_device", "bling_image_add_samples", "bling_image_develop_device", "bling_debug_set_image_budget",
+               "bling_image_add_windowed_device", "bling_image_add_windowed", "bling_image_scale_splats_device",
                "bling_destroy", "bling_last_error", "bling_version"]
 
 
@@ -334,6 +352,16 @@ def hip() -> C.CDLL:
         lib.bling_image_develop_device.argtypes = [C.c_void_p, C.POINTER(ImageDesc), C.POINTER(DevelopParams), C.c_void_p, C.c_void_p,
                                                    C.c_void_p]
         lib.bling_image_develop_device.restype = C.c_int
+        lib.bling_image_add_windowed_device.argtypes = [C.c_void_p, C.POINTER(ImageDesc), C.c_int, C.POINTER(ImageWindow),
+                                                        C.POINTER(C.c_uint64), C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                        C.c_void_p, C.c_void_p, C.POINTER(ImageStats)]
+        lib.bling_image_add_windowed_device.restype = C.c_int
+        lib.bling_image_add_windowed.argtypes = [C.c_void_p, C.POINTER(ImageDesc), C.c_int, C.POINTER(ImageWindow),
+                                                 C.POINTER(C.c_uint64), C.c_size_t, c_f32p, c_f32p, C.c_size_t, c_f32p, c_f32p,
+                                                 C.POINTER(ImageStats)]
+        lib.bling_image_add_windowed.restype = C.c_int
+        lib.bling_image_scale_splats_device.argtypes = [C.c_void_p, C.POINTER(ImageDesc), C.c_void_p, C.c_void_p, C.c_float]
+        lib.bling_image_scale_splats_device.restype = C.c_int
         lib.bling_debug_set_image_budget.argtypes = [C.c_void_p, C.c_size_t]
         lib.bling_debug_set_image_budget.restype = C.c_int
         lib.bling_debug_scene_info.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]

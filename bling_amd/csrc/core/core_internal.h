@@ -183,12 +183,18 @@ struct MergeState {
 
 // Image API state (image_ops.hip): per-sample results (X, Y, Z, valid) of one chunk, the per-tile counts,
 // segment starts, the scan's block sums and the (tile, sample) pair buffer, the drop / pair counters, the
-// host variant's staging buffers, and the pair budget (0: the default)
+// host variant's staging buffers, and the pair budget (0: the default).  The windowed calls add each sample's
+// window, the windows' sample offsets and cover rectangles, the carry image of a window cut by a chunk's end,
+// and the host variant's second staged image.
 struct ImageState {
   DBuf<float4> res;
   DBuf<uint32_t> cnt, start, sums, pairs;
   DBuf<unsigned long long> ctr;
   DBuf<float> xy, spectra, target;
+  DBuf<uint32_t> win;
+  DBuf<unsigned long long> first;
+  DBuf<int4> cover;
+  DBuf<float> carry, target2;
   size_t budget = 0;
 };
 

@@ -11,12 +11,15 @@
 // --film ordered (sampler scenes; the environment's BLING_FILM_ORDERED=1 means the same) forms every pass's film in
 // the reference's order without float atomics (BLING_PASS_ORDERED_FILM): the same files on every run.  The splat
 // renderers refuse it: their switch is --splat.
-//   bling --image-filters [--out DIR] [--size WxH] [--develop host|device] [--device D]
+//   bling --image-filters [--out DIR] [--size WxH] [--develop host|device] [--device D] [--windows N]
 // reproduces the reference's live command line (main = imageFilters, src/cmdline/Examples.hs:10-58) and is the whole
 // run: for box, gauss 3 3 2, mitchell 3 3 1/3 1/3, sinc 3 3 3 and triangle 3 3 it writes DIR/filter-show-<name>.png
 // (64 x 64, box film, red or green by the sign of evalFilter) and DIR/filter-test-<name>.png (480 x 270 unless --size
 // says otherwise, 25 offsets a pixel over the sample extent, |sin (150 r^2)| grey through rgbToSpectrumIllum).  The
 // samples are made on the host in row chunks and added on the device in order (bling_image_add_samples_device).
+// --windows N adds the test images' samples as a renderer does instead: the sample extent is cut into splitWindow's
+// 16 x 16 windows (Sampling.hs:55-58), each window's samples go to its own tile image and the tiles are added in
+// window order (bling_image_add_windowed_device, N windows a call); the files are the same for every N > 0.
 // With --develop device, or --splat ordered, such a scene's splat image (and an SPPM scene's film) lives on
 // the device for the whole run (bling_light_pass_device / bling_mlt_pass_device / bling_sppm_pass_device);
 // --develop device then develops it there (bling_film_develop_device) and only the developed pixels come back.
@@ -117,6 +120,8 @@ struct FilterImage {
   void *film = nullptr, *xy = nullptr, *spectra = nullptr, *out = nullptr;
   size_t cap = 0;                               // samples xy and spectra hold
   std::vector<float> hxy, hsp;
+  std::vector<bling_image_window> wins;           // --windows: the windows gathered so far and their sample offsets
+  std::vector<uint64_t> first;
   bling_image_stats total{};
   ~FilterImage() { (void)hipFree(film); (void)hipFree(xy); (void)hipFree(spectra); (void)hipFree(out); }
   bool start(const bling_filter& f, int w, int h) {
@@ -132,10 +137,16 @@ struct FilterImage {
     hsp.resize(hsp.size() + 16);
     bling_host_rgb_to_spectrum_illum(rgb, hsp.data() + hsp.size() - 16);
   }
-  // addSample' of the samples gathered so far, in order
+  // --windows: the samples gathered since the last call are those of window w
+  void end_window(const bling_image_window& w) {
+    if (first.empty()) first.push_back(0);
+    wins.push_back(w);
+    first.push_back(hxy.size() / 2);
+  }
+  // addSample' of the samples gathered so far, in order; with windows gathered, tile by tile (addTile)
   bool flush() {
     const size_t n = hxy.size() / 2;
-    if (n == 0) return true;
+    if (n == 0 && wins.empty()) return true;
     if (n > cap) {
       (void)hipFree(xy); (void)hipFree(spectra);
       xy = spectra = nullptr;
@@ -146,10 +157,14 @@ struct FilterImage {
         hipMemcpy(spectra, hsp.data(), n * 64, hipMemcpyHostToDevice) != hipSuccess)
       return false;
     bling_image_stats st;
-    if (bling_image_add_samples_device(ctx, &desc, BLING_IMAGE_ADD, xy, spectra, n, film, &st) != 0) {
+    const int rc = wins.empty() ? bling_image_add_samples_device(ctx, &desc, BLING_IMAGE_ADD, xy, spectra, n, film, &st)
+                                : bling_image_add_windowed_device(ctx, &desc, BLING_IMAGE_ADD, wins.data(), first.data(), wins.size(), xy,
+                                                                  spectra, n, film, nullptr, &st);
+    if (rc != 0) {
       std::fprintf(stderr, "%s\n", bling_last_error());
       return false;
     }
+    wins.clear(); first.clear();
     total.samples += st.samples; total.tile_pairs += st.tile_pairs; total.chunks += st.chunks; total.ms += st.ms;
     total.dropped_spectrum += st.dropped_spectrum; total.dropped_position += st.dropped_position;
     hxy.clear(); hsp.clear();
@@ -177,12 +192,17 @@ struct FilterImage {
 
 int image_filters(int argc, char** argv) {
   const char* dir = ".";
-  int width = 480, height = 270, device = 0;
+  int width = 480, height = 270, device = 0, windows = 0;
   bool dev_develop = false;
   for (int i = 2; i + 1 < argc; i += 2) {
     if (!std::strcmp(argv[i], "--out")) dir = argv[i + 1];
     else if (!std::strcmp(argv[i], "--device")) device = std::atoi(argv[i + 1]);
-    else if (!std::strcmp(argv[i], "--size")) {
+    else if (!std::strcmp(argv[i], "--windows")) {
+      if ((windows = std::atoi(argv[i + 1])) < 1) {
+        std::fprintf(stderr, "--windows takes a count of at least 1, not %s\n", argv[i + 1]);
+        return 2;
+      }
+    } else if (!std::strcmp(argv[i], "--size")) {
       if (std::sscanf(argv[i + 1], "%dx%d", &width, &height) != 2 || width < 1 || height < 1) {
         std::fprintf(stderr, "--size takes WxH, not %s\n", argv[i + 1]);
         return 2;
@@ -238,17 +258,33 @@ int image_filters(int argc, char** argv) {
       if (!img.start(flt, width, height)) { std::fprintf(stderr, "device film: allocation failed\n"); rc = 1; break; }
       bling_host_image_extent(&img.desc, e);
       const float sz = (float)std::min(width, height);
-      for (int py = e[2]; py <= e[3] && ok; ++py) {
-        for (int px = e[0]; px <= e[1]; ++px)
-          for (float sx : offs)
-            for (float sy : offs) {
-              const float x = (float)px + sx, y = (float)py + sy;
-              const float dx = x / sz - 0.5f, dy = 1.f - y / sz;
-              const float d = std::fabs(std::sin(150.f * (dx * dx + dy * dy)));
-              const float c[3] = {d, d, d};
-              img.sample(x, y, c);
-            }
-        if ((py - e[2]) % kRows == kRows - 1 || py == e[3]) ok = img.flush();
+      const auto pixel = [&](int px, int py) {
+        for (float sx : offs)
+          for (float sy : offs) {
+            const float x = (float)px + sx, y = (float)py + sy;
+            const float dx = x / sz - 0.5f, dy = 1.f - y / sz;
+            const float d = std::fabs(std::sin(150.f * (dx * dx + dy * dy)));
+            const float c[3] = {d, d, d};
+            img.sample(x, y, c);
+          }
+      };
+      if (windows > 0) {
+        // splitWindow (Sampling.hs:55-58) over the extent; a window's samples are its pixels', rows first
+        int k = 0;
+        for (int wy = e[2]; wy <= e[3] && ok; wy += 16)
+          for (int wx = e[0]; wx <= e[1] && ok; wx += 16) {
+            const bling_image_window w{wx, std::min(wx + 15, e[1]), wy, std::min(wy + 15, e[3])};
+            for (int py = w.y0; py <= w.y1; ++py)
+              for (int px = w.x0; px <= w.x1; ++px) pixel(px, py);
+            img.end_window(w);
+            if (++k % windows == 0) ok = img.flush();
+          }
+        ok = ok && img.flush();
+      } else {
+        for (int py = e[2]; py <= e[3] && ok; ++py) {
+          for (int px = e[0]; px <= e[1]; ++px) pixel(px, py);
+          if ((py - e[2]) % kRows == kRows - 1 || py == e[3]) ok = img.flush();
+        }
       }
       if (!ok || !img.write(base + "test-" + f.name + ".png")) { rc = 1; break; }
       std::printf("   filter-test-%s: %llu samples, %llu tile pairs, %llu chunks, %.2f ms on the device\n", f.name,
@@ -264,7 +300,7 @@ int image_filters(int argc, char** argv) {
 int main(int argc, char** argv) {
   if (argc < 2) {
     std::fprintf(stderr, "usage: %s scene.bling [--overrides S] [--passes N] [--out prefix] [--device D] [--develop host|device] [--splat atomic|ordered] [--film atomic|ordered]\n"
-                         "       %s --image-filters [--out DIR] [--size WxH] [--develop host|device] [--device D]\n", argv[0], argv[0]);
+                         "       %s --image-filters [--out DIR] [--size WxH] [--develop host|device] [--device D] [--windows N]\n", argv[0], argv[0]);
     return 2;
   }
   if (!std::strcmp(argv[1], "--image-filters")) return image_filters(argc, argv);

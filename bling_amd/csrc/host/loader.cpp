@@ -1576,6 +1576,109 @@ int bling_host_image_add_samples(const bling_image_desc* d, int op, const float*
   return 0;
 }
 
+int bling_host_image_tile(const bling_image_desc* d, const bling_image_window* wnd, bling_image_tile* out) {
+  using namespace bimgs;
+  if (!d || !wnd || !out) { g_err = "image: null argument"; return -1; }
+  const float fw = d->filter.width, fh = d->filter.height;
+  Tile t;
+  if (!(finite_f(fw) && finite_f(fh) && fw > 0.f && fh > 0.f) || !make_tile(wnd->x0, wnd->x1, wnd->y0, wnd->y1, fw, fh, &t)) {
+    g_err = "image: the window's tile has a width or height below 1";
+    return -1;
+  }
+  out->px = t.px; out->py = t.py; out->w = t.w; out->h = t.h;
+  // sampleExtent of the tile image (Image.hs:162-168)
+  out->extent[0] = t.px + (int32_t)std::floor(0.5f - fw);
+  out->extent[1] = (int32_t)((long long)t.px + (long long)std::floor(0.5f + (float)t.w + fw));
+  out->extent[2] = t.py + (int32_t)std::floor(0.5f - fh);
+  out->extent[3] = (int32_t)((long long)t.py + (long long)std::floor(0.5f + (float)t.h + fh));
+  return 0;
+}
+
+int bling_host_image_add_windowed(const bling_image_desc* d, int op, const bling_image_window* windows, const uint64_t* first,
+                                  size_t n_windows, const float* xy, const float* spectra, size_t n, float* film, float* splat,
+                                  bling_image_stats* st) {
+  using namespace bimgs;
+  if (st) *st = bling_image_stats{};
+  if (!d || !first || (n_windows && !windows) || (n && (!xy || !spectra))) { g_err = "image: null argument"; return -1; }
+  if (op != OP_ADD && op != OP_UNFILTERED && op != OP_SPLAT) { g_err = "image: unknown op"; return -1; }
+  if (!(op == OP_SPLAT ? splat : film)) { g_err = "image: the image the op writes is NULL"; return -1; }
+  const int w = d->width, h = d->height;
+  const float fw = d->filter.width, fh = d->filter.height;
+  if (w < 1 || h < 1 || !(finite_f(fw) && finite_f(fh) && fw > 0.f && fh > 0.f)) { g_err = "image: bad size or filter size"; return -1; }
+  if (first[0] != 0 || first[n_windows] != n) { g_err = "image: first must start at 0 and end at n"; return -1; }
+  std::vector<Rect> cover(n_windows);
+  for (size_t k = 0; k < n_windows; ++k) {
+    if (first[k] > first[k + 1]) { g_err = "image: first is not ascending"; return -1; }
+    Tile t;
+    if (!make_tile(windows[k].x0, windows[k].x1, windows[k].y0, windows[k].y1, fw, fh, &t)) {
+      g_err = "image: window " + std::to_string(k) + ": its tile has a width or height below 1";
+      return -1;
+    }
+    cover[k] = tile_cover(t, w, h);
+  }
+  const float ifw = 1.f / fw, ifh = 1.f / fw;                          // trap T12
+  const int nc = op == OP_SPLAT ? 3 : 4;
+  float* target = op == OP_SPLAT ? splat : film;
+  float* other = op == OP_SPLAT ? film : splat;
+  const int no = op == OP_SPLAT ? 4 : 3;
+  std::vector<float> tile;
+  bling_image_stats s{};
+  s.samples = n;
+  for (size_t k = 0; k < n_windows; ++k) {
+    // mkImageTile: the part of the zeroed tile image addTile reads, cw x ch pixels at (c.x0, c.y0)
+    const Rect c = cover[k];
+    const bool none = rect_empty(c);
+    const size_t cw = none ? 0 : (size_t)(c.x1 - c.x0 + 1), ch = none ? 0 : (size_t)(c.y1 - c.y0 + 1);
+    tile.assign(cw * ch * nc, 0.f);
+    for (size_t i = first[k]; i < first[k + 1]; ++i) {
+      const float sx = xy[2 * i], sy = xy[2 * i + 1], *b = spectra + 16 * i;
+      if (!position_ok(sx, sy)) { ++s.dropped_position; continue; }
+      if (!spectrum_ok(b)) { ++s.dropped_spectrum; continue; }
+      int x0, x1, y0, y1;
+      if (none || !sample_rect_in(op, sx, sy, fw, fh, w, h, c, &x0, &x1, &y0, &y1)) continue;
+      float X, Y, Z;
+      to_xyz(b, &X, &Y, &Z);
+      if (op == OP_SPLAT) {
+        float* o = tile.data() + 3 * ((size_t)(y0 - c.y0) * cw + (x0 - c.x0));
+        o[0] = o[0] + X; o[1] = o[1] + Y; o[2] = o[2] + Z;
+      } else if (op == OP_UNFILTERED) {
+        float* o = tile.data() + 4 * ((size_t)(y0 - c.y0) * cw + (x0 - c.x0));
+        o[0] = o[0] + 1.f; o[1] = o[1] + X; o[2] = o[2] + Y; o[3] = o[3] + Z;
+      } else {
+        const float dx = sx - 0.5f, dy = sy - 0.5f;
+        for (int y = y0; y <= y1; ++y)
+          for (int x = x0; x <= x1; ++x) {
+            const float fltw = d->filter.table[table_index(y, dy, ifh) * 16 + table_index(x, dx, ifw)];
+            float* o = tile.data() + 4 * ((size_t)(y - c.y0) * cw + (x - c.x0));
+            o[0] = o[0] + fltw; o[1] = o[1] + X * fltw; o[2] = o[2] + Y * fltw; o[3] = o[3] + Z * fltw;
+          }
+      }
+    }
+    // addTile: old + tile for every pixel of the tile inside the image, the zeros of the image the op left alone too
+    for (size_t y = 0; y < ch; ++y)
+      for (size_t x = 0; x < cw; ++x) {
+        const size_t p = (size_t)(c.y0 + (int)y) * w + (size_t)(c.x0 + (int)x);
+        const float* t = tile.data() + nc * (y * cw + x);
+        for (int q = 0; q < nc; ++q) target[nc * p + q] = target[nc * p + q] + t[q];
+        if (other)
+          for (int q = 0; q < no; ++q) other[no * p + q] = other[no * p + q] + 0.f;
+      }
+  }
+  if (st) *st = s;
+  return 0;
+}
+
+int bling_host_image_scale_splats(const bling_image_desc* d, float* splat, const float* factors, float scalar) {
+  if (!d || !splat) { g_err = "image: null argument"; return -1; }
+  if (d->width < 1 || d->height < 1) { g_err = "image: bad size"; return -1; }
+  const size_t px = (size_t)d->width * d->height;
+  for (size_t i = 0; i < px; ++i) {
+    const float s = factors ? factors[i] : scalar;
+    splat[3 * i] = splat[3 * i] * s; splat[3 * i + 1] = splat[3 * i + 1] * s; splat[3 * i + 2] = splat[3 * i + 2] * s;
+  }
+  return 0;
+}
+
 const char* bling_host_summary(const bling_host_scene* s) { return s ? s->b.summary.c_str() : ""; }
 void bling_host_free(bling_host_scene* s) { delete s; }
 const char* bling_host_last_error(void) { return g_err.c_str(); }

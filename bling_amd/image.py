@@ -9,6 +9,15 @@ caller computed, on a film that lives on the device.
 
 The film after add_samples is, bit for bit, what the reference's one thread makes of it by applying the op
 to the samples in order; host_add_samples is that sequential restatement on the CPU.  No scene is needed.
+
+A renderer that computes its samples in parallel windows uses its film as the reference's renderers do -- one
+mkImageTile image per SampleWindow, addTile in window order:
+
+    img.tile((0, 15, 0, 15))                  # the tile image's offset, size and sample extent
+    img.add_windowed(windows, counts, xy, spectra)   # window k owns counts[k] consecutive samples
+    img.scale_splats(1 / passes)              # scaleSplats; a zeroed tensor serves splitMImage
+
+host_add_windowed is the sequential restatement of add_windowed; the device equals it bit for bit.
 """
 from __future__ import annotations
 
@@ -99,6 +108,83 @@ def host_add_samples(filter, width, height, xy, spectra, op="add", target=None) 
     return target
 
 
+def image_tile(desc: _ffi.ImageDesc, window) -> dict:
+    """bling_host_image_tile: mkImageTile of the SampleWindow (x0, x1, y0, y1), ends inclusive -- the tile image's
+    offset ``px, py``, size ``w, h`` and its own sampleExtent ``extent``.  ValueError for a tile below 1 x 1."""
+    wnd, out = _ffi.ImageWindow(*(int(v) for v in window)), _ffi.ImageTile()
+    lib = _ffi.host()
+    if lib.bling_host_image_tile(C.byref(desc), C.byref(wnd), C.byref(out)) != 0:
+        raise ValueError(lib.bling_host_last_error().decode())
+    return {"px": out.px, "py": out.py, "w": out.w, "h": out.h, "extent": tuple(int(v) for v in out.extent)}
+
+
+def _windows(windows, counts_or_first, n):
+    """The ctypes window array and the n_windows + 1 ascending offsets; counts_or_first holds either the windows'
+    sample counts or those offsets."""
+    wl = [tuple(int(v) for v in w) for w in windows]
+    if any(len(w) != 4 for w in wl):
+        raise ValueError("a window is (x0, x1, y0, y1)")
+    c = np.asarray(counts_or_first, np.int64).reshape(-1)
+    if len(c) == len(wl):
+        if (c < 0).any():
+            raise ValueError("a window's sample count is negative")
+        first = np.concatenate([[0], np.cumsum(c)])
+    elif len(c) == len(wl) + 1:
+        first = c
+    else:
+        raise ValueError(f"{len(wl)} windows need {len(wl)} counts or {len(wl) + 1} offsets, not {len(c)}")
+    if (first < 0).any():
+        raise ValueError("a sample offset is negative")
+    arr = (_ffi.ImageWindow * max(1, len(wl)))(*(_ffi.ImageWindow(*w) for w in wl))
+    return arr, np.ascontiguousarray(first, np.uint64), len(wl)
+
+
+def _host_target(t, desc, per, what):
+    if not (isinstance(t, np.ndarray) and t.dtype == np.float32 and t.flags.c_contiguous and t.size == desc.width * desc.height * per):
+        raise ValueError(f"{what} must be a C-contiguous float32 array of {desc.width * desc.height * per} elements")
+    return t
+
+
+def host_add_windowed(filter, width, height, windows, counts_or_first, xy, spectra, op="add", film=None, splat=None, stats=None):
+    """bling_host_image_add_windowed: per window, in order, a zeroed mkImageTile image takes the op of the window's
+    samples and addTile adds it onto film (height x width x 4) and splat (height x width x 3), float32 arrays
+    accumulated into (zeros if None; pass False for an image that is to be left out, i.e. NULL).  Returns
+    (film, splat); stats, an _ffi.ImageStats, receives the counters."""
+    desc = filter if isinstance(filter, _ffi.ImageDesc) else image_desc(filter, width, height)
+    code = _op(op)
+    xy, spectra = _samples(xy, spectra)
+    arr, first, nw = _windows(windows, counts_or_first, len(xy))
+    if film is None:
+        film = np.zeros((desc.height, desc.width, 4), np.float32)
+    if splat is None:
+        splat = np.zeros((desc.height, desc.width, 3), np.float32)
+    fp = _ffi.f32ptr(_host_target(film, desc, 4, "film")) if film is not False else None
+    sp = _ffi.f32ptr(_host_target(splat, desc, 3, "splat")) if splat is not False else None
+    lib = _ffi.host()
+    st = stats if stats is not None else _ffi.ImageStats()
+    if lib.bling_host_image_add_windowed(C.byref(desc), code, arr, first.ctypes.data_as(C.POINTER(C.c_uint64)), nw, _ffi.f32ptr(xy),
+                                         _ffi.f32ptr(spectra), len(xy), fp, sp, C.byref(st)) != 0:
+        raise ValueError(lib.bling_host_last_error().decode())
+    return (None if film is False else film), (None if splat is False else splat)
+
+
+def host_scale_splats(desc: _ffi.ImageDesc, splat: np.ndarray, factors_or_scalar) -> np.ndarray:
+    """bling_host_image_scale_splats (scaleSplats) of a float32 height x width x 3 array, in place: a per-pixel
+    float32 array of factors, or one scalar."""
+    _host_target(splat, desc, 3, "splat")
+    lib = _ffi.host()
+    if np.ndim(factors_or_scalar) == 0:
+        rc = lib.bling_host_image_scale_splats(C.byref(desc), _ffi.f32ptr(splat), None, float(np.float32(factors_or_scalar)))
+    else:
+        f = np.ascontiguousarray(factors_or_scalar, np.float32)
+        if f.size != desc.width * desc.height:
+            raise ValueError(f"factors must hold {desc.width * desc.height} values")
+        rc = lib.bling_host_image_scale_splats(C.byref(desc), _ffi.f32ptr(splat), _ffi.f32ptr(f), 0.0)
+    if rc != 0:
+        raise ValueError(lib.bling_host_last_error().decode())
+    return splat
+
+
 class Image:
     """A film (W, X, Y, Z) and a splat image (X, Y, Z) on the device, written by the caller's samples.
     ``.film`` (height x width x 4) and ``.splat`` (height x width x 3) are torch float32 device tensors,
@@ -125,14 +211,10 @@ class Image:
         """bling_debug_set_image_budget (0: the default)."""
         _check(_ffi.hip().bling_debug_set_image_budget(self.ctx._h, int(max_tile_pairs)))
 
-    def add_samples(self, xy, spectra, op="add") -> _ffi.ImageStats:
-        """bling_image_add_samples_device: op "add" (addSample) or "add_unfiltered" into ``.film``, "splat"
-        into ``.splat``, the samples in order.  xy (n x 2) and spectra (n x 16) are numpy arrays, or torch
-        float32 tensors on this image's device, which are read in place.  The call runs on the context's own
-        stream and returns after completion: work of another stream on the tensors must have finished."""
+    def _device_samples(self, xy, spectra):
+        """xy and spectra as float32 tensors on this image's device (torch tensors are taken as they are, numpy
+        arrays are copied over) and the number of samples; the device has finished with them on return."""
         import torch
-        code = _op(op)
-        target = self.splat if op == "splat" else self.film
         if isinstance(xy, torch.Tensor) or isinstance(spectra, torch.Tensor):
             for t, what, per in ((xy, "xy", 2), (spectra, "spectra", 16)):
                 if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.ctx.device and t.dtype == torch.float32
@@ -141,12 +223,59 @@ class Image:
             n = xy.numel() // 2
             if spectra.numel() // 16 != n:
                 raise ValueError(f"{n} positions but {spectra.numel() // 16} spectra")
-            torch.cuda.synchronize(self.ctx.device)
         else:
             hx, hs = _samples(xy, spectra)
             n = len(hx)
             xy, spectra = torch.from_numpy(hx).to(self._dev), torch.from_numpy(hs).to(self._dev)
-            torch.cuda.synchronize(self.ctx.device)
+        torch.cuda.synchronize(self.ctx.device)
+        return xy, spectra, n
+
+    def tile(self, window) -> dict:
+        """mkImageTile of the SampleWindow (x0, x1, y0, y1): see image_tile."""
+        return image_tile(self.desc, window)
+
+    def add_windowed(self, windows, counts_or_first, xy, spectra, op="add") -> _ffi.ImageStats:
+        """bling_image_add_windowed_device: what a renderer does with its film -- per window (x0, x1, y0, y1), in
+        order, a zeroed tile image takes the op of the window's samples, and addTile adds it onto ``.film`` and
+        ``.splat``.  counts_or_first: the windows' sample counts, or the n_windows + 1 ascending offsets into the
+        sample list.  xy and spectra as for add_samples.  The result equals host_add_windowed bit for bit."""
+        code = _op(op)
+        xy, spectra, n = self._device_samples(xy, spectra)
+        arr, first, nw = _windows(windows, counts_or_first, n)
+        st = _ffi.ImageStats()
+        _check(_ffi.hip().bling_image_add_windowed_device(self.ctx._h, C.byref(self.desc), code, arr,
+                                                          first.ctypes.data_as(C.POINTER(C.c_uint64)), nw,
+                                                          C.c_void_p(xy.data_ptr() if n else None),
+                                                          C.c_void_p(spectra.data_ptr() if n else None), n,
+                                                          C.c_void_p(self.film.data_ptr()), C.c_void_p(self.splat.data_ptr()), C.byref(st)))
+        self.last_stats = st
+        return st
+
+    def scale_splats(self, factors_or_scalar):
+        """bling_image_scale_splats_device (scaleSplats): every pixel's three ``.splat`` values times its factor --
+        a height x width array (numpy, or a float32 tensor on this image's device) -- or times one scalar."""
+        import torch
+        if np.ndim(factors_or_scalar) == 0 and not isinstance(factors_or_scalar, torch.Tensor):
+            f, scalar = None, float(np.float32(factors_or_scalar))
+        else:
+            f, scalar = factors_or_scalar, 0.0
+            if not isinstance(f, torch.Tensor):
+                f = torch.from_numpy(np.ascontiguousarray(f, np.float32)).to(self._dev)
+            if not (f.is_cuda and f.device.index == self.ctx.device and f.dtype == torch.float32 and f.is_contiguous()
+                    and f.numel() == self.width * self.height):
+                raise ValueError(f"scale_splats: factors must be {self.width * self.height} contiguous float32 values on {self._dev}")
+        torch.cuda.synchronize(self.ctx.device)
+        _check(_ffi.hip().bling_image_scale_splats_device(self.ctx._h, C.byref(self.desc), C.c_void_p(self.splat.data_ptr()),
+                                                          C.c_void_p(f.data_ptr() if f is not None else None), scalar))
+
+    def add_samples(self, xy, spectra, op="add") -> _ffi.ImageStats:
+        """bling_image_add_samples_device: op "add" (addSample) or "add_unfiltered" into ``.film``, "splat"
+        into ``.splat``, the samples in order.  xy (n x 2) and spectra (n x 16) are numpy arrays, or torch
+        float32 tensors on this image's device, which are read in place.  The call runs on the context's own
+        stream and returns after completion: work of another stream on the tensors must have finished."""
+        code = _op(op)
+        target = self.splat if op == "splat" else self.film
+        xy, spectra, n = self._device_samples(xy, spectra)
         st = _ffi.ImageStats()
         _check(_ffi.hip().bling_image_add_samples_device(self.ctx._h, C.byref(self.desc), code, C.c_void_p(xy.data_ptr() if n else None),
                                                          C.c_void_p(spectra.data_ptr() if n else None), n,
@@ -176,5 +305,5 @@ class Image:
         return out
 
 
-__all__ = ["Image", "host_add_samples", "make_filter", "eval_filter", "image_desc", "image_extent", "rgb_to_spectrum_illum",
+__all__ = ["Image", "host_add_samples", "host_add_windowed", "host_scale_splats", "image_tile","make_filter", "eval_filter", "image_desc", "image_extent", "rgb_to_spectrum_illum",
            "BlingError"]

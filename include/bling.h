@@ -577,21 +577,58 @@ int bling_debug_splat_times(bling_ctx* ctx, double* ms_kernel, double* ms_merge)
  * bling_image_add_samples: the three are host buffers, staged through device buffers the context owns.
  * bling_image_develop_device: bling_film_develop_device with the width and height of the desc instead of an
  *   uploaded scene's: the same three formats, window rule and overlap check; no scene needed. */
-/* bling_image_desc and the BLING_IMAGE_* ops: bling_scene.h, shared with the host library */
-typedef struct bling_image_stats {
-    uint64_t samples;          /* n                                                              */
-    uint64_t dropped_spectrum; /* samples dropped for a NaN / infinite band                      */
-    uint64_t dropped_position; /* samples dropped for a non-finite or huge position              */
-    uint64_t tile_pairs;       /* (destination tile, sample) pairs written                       */
-    uint64_t chunks;           /* chunks the list was cut into                                   */
-    double   ms;               /* device time of the call (HIP events)                           */
-} bling_image_stats;
+/* bling_image_desc, bling_image_stats, bling_image_window and the BLING_IMAGE_* ops: bling_scene.h, shared with the
+ * host library */
 int bling_image_add_samples_device(bling_ctx* ctx, const bling_image_desc* desc, int op, const void* xy_dev,
                                    const void* spectra_dev, size_t n, void* target_dev, bling_image_stats* stats);
 int bling_image_add_samples(bling_ctx* ctx, const bling_image_desc* desc, int op, const float* xy, const float* spectra,
                             size_t n, float* target_host, bling_image_stats* stats);
 int bling_image_develop_device(bling_ctx* ctx, const bling_image_desc* desc, const bling_develop_params* p,
                                const void* film_dev, const void* splat_dev, void* out_dev);
+/* ---- the image API on tiles: a renderer's windows onto the film, in order ----
+ * Replaces: mkImageTile, addTile and scaleSplats of Image.hs (:108-120, :178-199, :93-106) as every renderer of
+ * the reference uses them: prender (Rendering.hs:118-134) and SPPM's eye pass (SPPM.hs:148-163) make one
+ * mkImageTile image per SampleWindow, add that window's samples to it and then addTile the tiles onto the image
+ * in window order.  A host-side Renderer that computes its own samples in parallel windows reproduces the
+ * reference's film through these calls.  Like the calls above they need no scene and leave one untouched.
+ *   windows: n_windows SampleWindows (host array, ends inclusive); first: n_windows + 1 ascending sample
+ *   offsets (host array) from 0 to n -- window k owns samples first[k] .. first[k+1]-1; xy, spectra: as above.
+ *   film: width*height*4 floats, splat: width*height*3 floats.  Either may be NULL, except the one the op
+ *   writes; a NULL image is not touched at all.
+ * The promise: film and splat after the call equal, bit for bit, bling_host_image_add_windowed (bling_host.h)
+ * of the same arguments, and are the same bytes on every run; no float atomic is used.  For k = 0, 1, ... in
+ * order: a zeroed tile image (offset px = max 0 x0, py = max 0 y0, size w = x1 - px + floor (0.5 + fw), h
+ * likewise -- a tile does not extend to the left of or above its window) receives the op of the window's
+ * samples in ascending index, clipped to the tile (addSample: x0 = max px (ceiling (dx - fw)), x1 = min (px + w
+ * - 1) (floor (dx + fw)); the unfiltered ops: floor sx - px in [0, w)); then every tile pixel inside the image
+ * does old + tile on the three splat and the four film channels.  So a pixel's value is ((old + T_0) + T_1) + ...
+ * over the windows whose tile covers it, T_k summed from +0 -- not the flat list's sample-by-sample sum, and not
+ * its pixels either.  This holds for any windows: overlapping, nested, repeated, partly or wholly outside the
+ * image, or empty (first[k] == first[k+1]).  Calls compose: windows 0 .. k in one call and k+1 .. in the next
+ * give the bits of one call.
+ * Trap T36: addTile adds a tile's zeros too, so a film or splat value of -0.0 under any window's tile becomes
+ * +0.0 even if no sample reached it; a pixel under no tile keeps its bits.
+ * The drop rules and counters are those above: a dropped sample is counted whether or not it lies in its tile; a
+ * sample outside its own window's tile is clipped, not counted.  Chunks (the pair budget above) end at window
+ * boundaries; a window longer than the budget is cut inside and its partial tile image carried to the next
+ * chunk, so a window's sum is never split into two film additions.
+ * Errors (BLING_EINVAL, nothing written): those above; a NULL windows / first; a first that does not start at
+ * 0, ascend, and end at n; a window whose tile has w < 1 or h < 1 (the reference's MV.replicate of a negative
+ * length; also beyond 2^31 - 1); film overlapping splat, or either overlapping xy or spectra.
+ * bling_image_add_windowed_device: xy, spectra, film and splat are device buffers on device_ids[0].
+ * bling_image_add_windowed: the four are host buffers, staged through device buffers the context owns.
+ * bling_image_scale_splats_device: scaleSplats -- every pixel's three splat values become v * s, one binary32
+ *   product each, s = factors_dev[i] (width*height floats on the device) or scalar when factors_dev is NULL.
+ * splitMImage (Image.hs:84-91) is a zeroed image of the same shape: hipMemset of a buffer, or
+ *   torch.zeros_like, serves it; there is no entry point. */
+int bling_image_add_windowed_device(bling_ctx* ctx, const bling_image_desc* desc, int op, const bling_image_window* windows,
+                                    const uint64_t* first, size_t n_windows, const void* xy_dev, const void* spectra_dev, size_t n,
+                                    void* film_dev, void* splat_dev, bling_image_stats* stats);
+int bling_image_add_windowed(bling_ctx* ctx, const bling_image_desc* desc, int op, const bling_image_window* windows,
+                             const uint64_t* first, size_t n_windows, const float* xy, const float* spectra, size_t n,
+                             float* film_host, float* splat_host, bling_image_stats* stats);
+int bling_image_scale_splats_device(bling_ctx* ctx, const bling_image_desc* desc, void* splat_dev, const void* factors_dev,
+                                    float scalar);
 /* Test hook: the pair budget of this context's image calls, in pairs; 0 restores the default (64 MiB). */
 int bling_debug_set_image_budget(bling_ctx* ctx, size_t max_tile_pairs);
 

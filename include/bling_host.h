@@ -109,6 +109,29 @@ void  bling_host_image_extent(const bling_image_desc* desc, int32_t out4[4]);
  * filter size that is not finite and positive. */
 int   bling_host_image_add_samples(const bling_image_desc* desc, int op, const float* xy, const float* spectra, size_t n,
                                    float* target);
+/* mkImageTile (Image.hs:108-120) of a SampleWindow over the image: the tile image's offset, size and
+ * sampleExtent (Image.hs:162-168 with the offset), literally: px = max 0 x0, w = x1 - px + floor (0.5 + fw) -- a
+ * tile does not extend to the left of or above its window.  0, or -1 for a NULL argument or a tile with w < 1 or
+ * h < 1 (the reference's MV.replicate of a negative length). */
+int   bling_host_image_tile(const bling_image_desc* desc, const bling_image_window* window, bling_image_tile* out);
+/* The sequential binary32 restatement of a renderer's use of its film (prender, Rendering.hs:118-134): for
+ * window k = 0 .. n_windows-1 in order, a zeroed mkImageTile image of windows[k] receives op of samples
+ * first[k] .. first[k+1]-1 in ascending index with the tile's offset (addSample's x0 = max ox (ceiling (dx - fw)),
+ * x1 = min (ox + w - 1) (floor (dx + fw)); the unfiltered ops' floor sx - ox in [0, w)), and addTile
+ * (Image.hs:178-199) then adds the tile onto film AND splat: old + tile for every tile pixel inside the image,
+ * the tile's zeros too (trap T36: a -0.0 under a tile becomes +0.0).  first: n_windows + 1 ascending offsets
+ * from 0 to n.  film (width*height*4) or splat (width*height*3) may be NULL, except the one the op writes; a
+ * NULL image is not touched by addTile either.  stats (may be NULL): samples and the two drop counters of
+ * bling.h's rules.  bling_image_add_windowed[_device] gives the same bits.  0, or -1 for a NULL argument, an
+ * unknown op, a bad size or filter size, a first that does not ascend from 0 to n, or a window whose tile has
+ * w < 1 or h < 1; the images are then untouched. */
+int   bling_host_image_add_windowed(const bling_image_desc* desc, int op, const bling_image_window* windows, const uint64_t* first,
+                                    size_t n_windows, const float* xy, const float* spectra, size_t n, float* film, float* splat,
+                                    bling_image_stats* stats);
+/* scaleSplats (Image.hs:93-106): every pixel's three splat values become v * s, one binary32 product each,
+ * s = factors[i] of pixel i, or scalar when factors is NULL.  splitMImage (Image.hs:84-91) is a zeroed image of
+ * the same shape and needs no call. */
+int   bling_host_image_scale_splats(const bling_image_desc* desc, float* splat, const float* factors, float scalar);
 /* rgbToSpectrumIllum (Spectrum.hs:146-159 over the illuminant bases), as the loader applies it to image maps. */
 void  bling_host_rgb_to_spectrum_illum(const float rgb[3], float out16[16]);
 

@@ -265,6 +265,24 @@ typedef struct bling_image_desc {
 #define BLING_IMAGE_ADD            0   /* addSample            (Image.hs:250-299) -> film, 4 floats a pixel  */
 #define BLING_IMAGE_ADD_UNFILTERED 1   /* addUnfilteredSample  (Image.hs:223-246) -> film                     */
 #define BLING_IMAGE_SPLAT          2   /* splatSample          (Image.hs:201-221) -> splat image, 3 floats    */
+/* what an image call reports (bling_image_add_*; the host library fills the first three) */
+typedef struct bling_image_stats {
+    uint64_t samples;          /* n                                                              */
+    uint64_t dropped_spectrum; /* samples dropped for a NaN / infinite band                      */
+    uint64_t dropped_position; /* samples dropped for a non-finite or huge position              */
+    uint64_t tile_pairs;       /* (destination tile, sample) pairs written                       */
+    uint64_t chunks;           /* chunks the list was cut into                                   */
+    double   ms;               /* device time of the call (HIP events)                           */
+} bling_image_stats;
+/* A SampleWindow (Sampling.hs), both ends inclusive, and the tile image mkImageTile (Image.hs:108-120) makes
+ * for it: its offset (px, py) in the film, its size, and its own sampleExtent (Image.hs:162-168). */
+typedef struct bling_image_window {
+    int32_t x0, x1, y0, y1;
+} bling_image_window;
+typedef struct bling_image_tile {
+    int32_t px, py, w, h;      /* px = max 0 x0, w = x1 - px + floor (0.5 + fw); likewise py, h       */
+    int32_t extent[4];         /* x0, x1, y0, y1 of sampleExtent with the offset, inclusive          */
+} bling_image_tile;
 
 /* ---- renderer configuration (IO/RendererParser.hs, IO/IntegratorParser.hs) ---- */
 enum bling_sampler_kind { BLING_SAMPLER_STRATIFIED = 0, BLING_SAMPLER_RANDOM = 1 };
