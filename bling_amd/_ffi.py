@@ -157,6 +157,15 @@ class ImageStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LiStats(C.Structure):
+    """bling_li_stats (include/bling.h)."""
+    _fields_ = [("rays", C.c_uint64), ("dropped", C.c_uint64), ("rays_continuation", C.c_uint64), ("rays_mis", C.c_uint64),
+                ("rays_shadow", C.c_uint64), ("path_vertices", C.c_uint64), ("waves", C.c_uint64), ("ms_total", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class RenderConfig(C.Structure):
     _fields_ = [("renderer", C.c_int32), ("sampler", C.c_int32), ("nu", C.c_int32), ("nv", C.c_int32),
                 ("spp", C.c_int32), ("max_depth", C.c_int32), ("sample_depth", C.c_int32),
@@ -235,6 +244,7 @@ HIP_SYMBOLS = ["bling_create", "bling_scene_upload", "bling_scene_validate", "bl
                "bling_film_develop", "bling_film_develop_device", "bling_light_pass", "bling_debug_light_records", "bling_mlt_pass", "bling_debug_mlt_records", "bling_debug_mlt_boot", "bling_debug_mlt_set_boot", "bling_light_pass_device", "bling_mlt_pass_device", "bling_debug_splat_merge", "bling_debug_set_splat_budget", "bling_debug_splat_times", "bling_sppm_pass_device", "bling_debug_sppm_records", "bling_debug_bidir_terms",
                "bling_image_add_samples_device", "bling_image_add_samples", "bling_image_develop_device", "bling_debug_set_image_budget",
                "bling_image_add_windowed_device", "bling_image_add_windowed", "bling_image_scale_splats_device",
+               "bling_surface_li_device", "bling_surface_li", "bling_debug_set_li_chunk",
                "bling_destroy", "bling_last_error", "bling_version"]
 
 
@@ -364,6 +374,15 @@ def hip() -> C.CDLL:
         lib.bling_image_scale_splats_device.restype = C.c_int
         lib.bling_debug_set_image_budget.argtypes = [C.c_void_p, C.c_size_t]
         lib.bling_debug_set_image_budget.restype = C.c_int
+        if hasattr(lib, "bling_surface_li_device"):   # older experiment builds lack the integrator seam
+            lib.bling_surface_li_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                    C.c_void_p, C.POINTER(LiStats)]
+            lib.bling_surface_li_device.restype = C.c_int
+            lib.bling_surface_li.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, c_f32p, c_u32p, C.c_size_t, c_f32p,
+                                             C.POINTER(LiStats)]
+            lib.bling_surface_li.restype = C.c_int
+            lib.bling_debug_set_li_chunk.argtypes = [C.c_void_p, C.c_size_t]
+            lib.bling_debug_set_li_chunk.restype = C.c_int
         lib.bling_debug_scene_info.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
         lib.bling_debug_scene_info.restype = C.c_int
         if hasattr(lib, "bling_debug_mis_culled"):    # older experiment builds lack it

@@ -198,6 +198,17 @@ struct ImageState {
   size_t budget = 0;
 };
 
+// The integrator seam for a caller's rays (li_rays.hip): a wave's 16-band records, its dropped flags, the
+// dropped counter, the host variant's staging buffers, and the debug chunk (0: the default).
+struct LiState {
+  DBuf<float4> lfull;
+  DBuf<uint8_t> drop;
+  DBuf<unsigned long long> ctr;
+  DBuf<float> rays, L;
+  DBuf<uint32_t> ids;
+  size_t chunk = 0;
+};
+
 }  // namespace bcore
 
 struct bling_ctx;
@@ -360,6 +371,7 @@ struct bling_ctx {
   std::vector<std::unique_ptr<DBuf<float>>> stage;  // primary: landing buffer of peer j's tile images
   MergeState merge;                // the ordered splat merge (splat_merge.h)
   ImageState image;                // the image API (image_ops.hip)
+  LiState li;                      // the integrator seam for a caller's rays (li_rays.hip)
 
   ~bling_ctx() {
     peers.clear();                          // each peer frees its memory on its own device

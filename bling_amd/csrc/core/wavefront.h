@@ -1485,18 +1485,15 @@ static __global__ __launch_bounds__(256) void k_resolve(const DevScene* __restri
 // ------------------------------------------------------------------ camera rays
 struct TileDesc { int x0, x1, y0, y1; uint32_t offset, count; };
 
-// camera sample i (raygen order = sample id = slot of the current set)
-DEV void init_path(const DevScene& S, const WaveState& W, uint32_t i, int ix, int iy, uint32_t n, uint32_t seed,
-                   uint32_t pass) {
-  uint32_t pixel = (uint32_t)((iy - S.ey0) * S.ext_w + (ix - S.ex0));
-  SampleKey k = sample_key(seed, pass, pixel, n);
-  float ox, oy, lu, lv;
-  camera_sample(S, k, &ox, &oy, &lu, &lv);
-  float imx = (float)ix + ox, imy = (float)iy + oy;
-  Ray r = fire_ray(S.camera, imx, imy, lu, lv);
+// What follows fireRay: slot i of the current set starts the path of sample n of stream `pixel` along r
+// (tmax = infinity).  The camera's rays (init_path) and a caller's (li_rays.h k_li_intake) share it.
+// miss: the ray is made with the kd_root flag's "rejected" encoding whatever the test says, so no
+// traversal kernel walks it (a caller's ray that can hit nothing, or the stand-in of a dropped one).
+DEV void init_path_ray(const DevScene& S, const WaveState& W, uint32_t i, const Ray& r, uint32_t pixel, uint32_t n,
+                       bool miss = false) {
   const float4 ro = make_float4(r.o.x, r.o.y, r.o.z, r.tmin);
   W.cur.org[i] = ro;
-  W.cur.dir[i] = make_float4(r.d.x, r.d.y, r.d.z, kd_flag_w(0.f, kd_root(S, r)));   // kd_root flag (dev_trace.h)
+  W.cur.dir[i] = make_float4(r.d.x, r.d.y, r.d.z, kd_flag_w(0.f, kd_root(S, r) && !miss));   // kd_root flag (dev_trace.h)
   W.cur.meta[i] = make_uint4(VF_SPEC, pixel, n, i);                     // the camera "bounce" is specular (Path.hs:38)
   if (W.dl_mask) {
     // DirectLighting keeps T and L in its one set (the Path pipeline takes the camera path's T = 1
@@ -1506,10 +1503,22 @@ DEV void init_path(const DevScene& S, const WaveState& W, uint32_t i, int ix, in
     store_sp(W.cur.T, i, sconst(1.f));
     store_sp(W.cur.L, i, sconst(0.f));
   }
-  W.img[i] = make_float2(imx, imy);
   W.result[i] = make_float4(0.f, 0.f, 0.f, 0.f);
   W.queue[Q_SHADE0][i] = i;
   W.queue[Q_CLOSEST][i] = (i << 1) | ENTRY_CONT;
+}
+
+// camera sample i (raygen order = sample id = slot of the current set)
+DEV void init_path(const DevScene& S, const WaveState& W, uint32_t i, int ix, int iy, uint32_t n, uint32_t seed,
+                   uint32_t pass) {
+  uint32_t pixel = (uint32_t)((iy - S.ey0) * S.ext_w + (ix - S.ex0));
+  SampleKey k = sample_key(seed, pass, pixel, n);
+  float ox, oy, lu, lv;
+  camera_sample(S, k, &ox, &oy, &lu, &lv);
+  float imx = (float)ix + ox, imy = (float)iy + oy;
+  Ray r = fire_ray(S.camera, imx, imy, lu, lv);
+  init_path_ray(S, W, i, r, pixel, n);
+  W.img[i] = make_float2(imx, imy);
 }
 
 // Slot order of a tile's camera samples (DevScene::sample_major).  Pixel-major (slot = pixel x spp

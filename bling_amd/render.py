@@ -352,6 +352,60 @@ class Context:
                                    _ffi.f32ptr(L), _ffi.f32ptr(img), C.byref(st)))
         return L, img, st
 
+    def surface_li(self, rays, ids, seed=DEFAULT_SEED, pass_index=0, out=None):
+        """bling_surface_li_device: the uploaded scene's integrator (path, directLighting or debug normals) along
+        the caller's rays, without a host copy.  rays: a float32 tensor (7, n) on this context's first device --
+        the planes ox, oy, oz, dx, dy, dz, tmin; tmax is infinite and the direction is used as given.  ids: an
+        int32 or uint32 tensor (n, 2) of (pixel, n): the ray draws from the stream of sample n of stream `pixel`
+        (the built-in camera's, for extent pixel (ix, iy): pixel = (iy - ey0) * ext_w + (ix - ex0)).  Returns
+        (L, LiStats): L a float32 device tensor (n, 16) -- out, if given -- in the layout Image.add_samples and
+        Image.add_windowed take as spectra.  A ray with a NaN or infinite float (tmin = +inf excepted), a zero
+        direction or n >= spp is dropped: zeros, counted in LiStats.dropped.  The call runs on the context's own
+        stream and returns after completion: work of another stream on the tensors must have finished."""
+        import torch
+        dev = f"cuda:{self.device}"
+        id_types = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
+        for t, what, types in ((rays, "rays", (torch.float32,)), (ids, "ids", id_types)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.device and t.dtype in types
+                    and t.is_contiguous()):
+                raise ValueError(f"surface_li: {what} must be a contiguous {' or '.join(str(d) for d in types)} tensor on {dev}")
+        if rays.dim() != 2 or rays.shape[0] != 7:
+            raise ValueError(f"surface_li: rays must be (7, n), got {tuple(rays.shape)}")
+        n = int(rays.shape[1])
+        if ids.dim() != 2 or tuple(ids.shape) != (n, 2):
+            raise ValueError(f"surface_li: ids must be ({n}, 2), got {tuple(ids.shape)}")
+        if out is None:
+            out = torch.empty((n, 16), dtype=torch.float32, device=dev)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device.index == self.device and out.dtype == torch.float32
+                  and out.is_contiguous() and out.numel() == n * 16):
+            raise ValueError(f"surface_li: out must be a contiguous float32 tensor of {n * 16} elements on {dev}")
+        torch.cuda.synchronize(self.device)
+        st = _ffi.LiStats()
+        _check(_ffi.hip().bling_surface_li_device(self._h, seed, pass_index, C.c_void_p(rays.data_ptr() if n else None),
+                                                  C.c_void_p(ids.data_ptr() if n else None), n,
+                                                  C.c_void_p(out.data_ptr() if n else None), C.byref(st)))
+        return out, st
+
+    def host_surface_li(self, rays: np.ndarray, ids: np.ndarray, seed=DEFAULT_SEED, pass_index=0):
+        """bling_surface_li: surface_li for numpy arrays -- rays float32 (7, n), ids (n, 2) of (pixel, n) --
+        staged through device buffers the context owns.  Returns (L (n, 16) float32, LiStats)."""
+        rays = np.ascontiguousarray(rays, np.float32)
+        if rays.ndim != 2 or rays.shape[0] != 7:
+            raise ValueError(f"host_surface_li: rays must be (7, n), got {rays.shape}")
+        n = rays.shape[1]
+        ids = np.ascontiguousarray(np.asarray(ids).astype(np.uint32, copy=False)).reshape(-1, 2)
+        if len(ids) != n:
+            raise ValueError(f"host_surface_li: {n} rays but {len(ids)} id pairs")
+        L = np.zeros((n, 16), np.float32)
+        st = _ffi.LiStats()
+        _check(_ffi.hip().bling_surface_li(self._h, seed, pass_index, _ffi.f32ptr(rays) if n else None,
+                                           _ffi.u32ptr(ids) if n else None, n, _ffi.f32ptr(L) if n else None, C.byref(st)))
+        return L, st
+
+    def set_li_chunk(self, max_rays=0):
+        """bling_debug_set_li_chunk: the rays per wave of surface_li / host_surface_li (0: the default)."""
+        _check(_ffi.hip().bling_debug_set_li_chunk(self._h, int(max_rays)))
+
     def bidir_terms(self, samples: np.ndarray, seed=DEFAULT_SEED, pass_index=0):
         """bling_debug_bidir_terms: (terms (k, 3, 16) = ld, le, l of BidirPath's contrib, lens (k, 4) =
         eye length, light length, eye and light specular masks) of the (x, y, n) samples."""

@@ -632,6 +632,54 @@ int bling_image_scale_splats_device(bling_ctx* ctx, const bling_image_desc* desc
 /* Test hook: the pair budget of this context's image calls, in pairs; 0 restores the default (64 MiB). */
 int bling_debug_set_image_budget(bling_ctx* ctx, size_t max_tile_pairs);
 
+/* ---- the integrator seam: surfaceLi for the caller's rays, on device buffers ----
+ * Replaces: SurfaceIntegrator.surfaceLi :: Scene -> Ray -> Sampled s Spectrum (Integrator.hs:32-36) as every
+ * renderer of the reference calls it, with a ray it made itself.  bling_sample_li always fires the uploaded
+ * scene's own camera; these calls take the rays from the caller -- its own camera model, or any rays along which
+ * it wants radiance -- and return the spectra in the layout bling_image_add_samples_device and
+ * bling_image_add_windowed_device take as `spectra`, so that caller's rays -> surfaceLi -> addSample / addTile ->
+ * develop runs on the device end to end.
+ *   rays_soa: 7 planes of n floats: ox, oy, oz, dx, dy, dz, tmin.  tmax is +infinity, as fireRay's
+ *     (Camera.hs:49-76).  The direction is used as given: the caller normalises, as fireRay does.
+ *   ids: 2 uint32 per ray, (pixel, n): the ray's random stream is that of sample n of stream `pixel` of the pass,
+ *     sample_key(seed, pass_index, pixel, n).  The camera's dimensions are simply not drawn; the path's
+ *     dimensions keep the indices they have after a camera sample.  The built-in camera's stream for sample n of
+ *     extent pixel (ix, iy) is pixel = (iy - ey0) * ext_w + (ix - ex0), with (ex0, ey0) the sample extent's
+ *     first pixel and ext_w its width: a ray equal to that camera ray, with those ids, gives bling_sample_li's
+ *     spectrum bit for bit.  Any pixel value is a valid stream; n must be below the scene's spp.
+ *   L: n x 16 floats, row-major, ray k at 16 k: the spectrum before addSample's NaN filter, as bling_sample_li
+ *     gives it.
+ * The radiance is that of the integrator desc->config.integrator selected at upload: `path`, `directLighting` or
+ * `debug normals`.  A ray's 16 floats depend on its seven floats, its ids, the seed and the pass only: not on n,
+ * on its position in the batch, on what else is in the batch, or on how the call is cut into waves.
+ * Dropped rays: a ray with a NaN or infinite float (tmin = +infinity excepted: a valid ray that misses
+ * everything), with an all-zero direction, or with n >= spp is not traced.  It writes sixteen +0.0, counts in
+ * stats->dropped and changes nothing for any other ray.
+ * The call cuts itself into waves of at most the context's path capacity (at least 2^22 rays;
+ * bling_debug_set_li_chunk sets another bound): any n is served, stats->waves is their number.
+ * Errors: BLING_EINVAL for a NULL ctx; BLING_ENOSCENE without a scene; BLING_EINVAL when the scene's renderer
+ * is not `sampler`; BLING_EUNSUPPORTED for the `bidir` integrator (its walk kernels make their camera ray
+ * inside); then n == 0 is BLING_OK; BLING_EINVAL for a NULL rays_soa / ids / L, or an L that overlaps either
+ * input.  Not served: a finite tmax.  stats may be NULL.
+ * bling_surface_li_device: the three buffers are device buffers on device_ids[0] (e.g. torch tensors'
+ *   data_ptr()); nothing is staged through the host.  The call runs on the context's stream and returns after
+ *   completion; a multi-device context runs it on device_ids[0], as bling_sample_li.
+ * bling_surface_li: the three are host buffers, staged through device buffers the context owns. */
+typedef struct bling_li_stats {
+    uint64_t rays;              /* rays handed in                                                   */
+    uint64_t dropped;           /* rays not traced (see above); their L is +0                       */
+    uint64_t rays_continuation, rays_mis, rays_shadow, path_vertices;   /* as bling_stats; a dropped
+                                   ray is no vertex                                                 */
+    uint64_t waves;             /* chunks the call was cut into                                     */
+    double   ms_total;          /* device time of the call (HIP events)                             */
+} bling_li_stats;
+int bling_surface_li_device(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, const void* rays_soa_dev,
+                            const void* ids_dev, size_t n, void* L_dev, bling_li_stats* stats);
+int bling_surface_li(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, const float* rays_soa, const uint32_t* ids,
+                     size_t n, float* L_out, bling_li_stats* stats);
+/* Test hook: the rays per wave of this context's bling_surface_li* calls; 0 restores the default. */
+int bling_debug_set_li_chunk(bling_ctx* ctx, size_t max_rays);
+
 /* Diagnostics (no reference counterpart): the path-state bytes the shading kernel k_shade moved in
  * the context's last bling_render_pass*, per stream and direction -- out[2 k] read, out[2 k + 1]
  * written, stream k in the order BLING_STREAM_NAMES lists -- counted where the algorithm needs
