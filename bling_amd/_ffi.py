@@ -166,6 +166,14 @@ class LiStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CameraStats(C.Structure):
+    """bling_camera_stats (include/bling.h)."""
+    _fields_ = [("samples", C.c_uint64), ("windows", C.c_uint64), ("ms_total", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class RenderConfig(C.Structure):
     _fields_ = [("renderer", C.c_int32), ("sampler", C.c_int32), ("nu", C.c_int32), ("nv", C.c_int32),
                 ("spp", C.c_int32), ("max_depth", C.c_int32), ("sample_depth", C.c_int32),
@@ -231,6 +239,9 @@ def host() -> C.CDLL:
         lib.bling_host_image_add_windowed.restype = C.c_int
         lib.bling_host_image_scale_splats.argtypes = [C.POINTER(ImageDesc), c_f32p, c_f32p, C.c_float]
         lib.bling_host_image_scale_splats.restype = C.c_int
+        lib.bling_host_camera_samples.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(ImageWindow), C.POINTER(C.c_uint64),
+                                                  C.c_size_t, c_f32p, c_u32p, c_f32p, c_f32p]
+        lib.bling_host_camera_samples.restype = C.c_int
         lib.bling_host_rgb_to_spectrum_illum.argtypes = [c_f32p, c_f32p]
         lib.bling_host_rgb_to_spectrum_illum.restype = None
         _host = lib
@@ -245,6 +256,7 @@ HIP_SYMBOLS = ["bling_create", "bling_scene_upload", "bling_scene_validate", "bl
                "bling_image_add_samples_device", "bling_image_add_samples", "bling_image_develop_device", "bling_debug_set_image_budget",
                "bling_image_add_windowed_device", "bling_image_add_windowed", "bling_image_scale_splats_device",
                "bling_surface_li_device", "bling_surface_li", "bling_debug_set_li_chunk",
+               "bling_camera_samples_device", "bling_camera_samples",
                "bling_destroy", "bling_last_error", "bling_version"]
 
 
@@ -383,6 +395,14 @@ def hip() -> C.CDLL:
             lib.bling_surface_li.restype = C.c_int
             lib.bling_debug_set_li_chunk.argtypes = [C.c_void_p, C.c_size_t]
             lib.bling_debug_set_li_chunk.restype = C.c_int
+        if hasattr(lib, "bling_camera_samples_device"):   # older experiment builds lack the sampler and camera seam
+            lib.bling_camera_samples_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(ImageWindow),
+                                                        C.POINTER(C.c_uint64), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.POINTER(CameraStats)]
+            lib.bling_camera_samples_device.restype = C.c_int
+            lib.bling_camera_samples.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(ImageWindow), C.POINTER(C.c_uint64),
+                                                 C.c_size_t, c_f32p, c_u32p, c_f32p, c_f32p, C.POINTER(CameraStats)]
+            lib.bling_camera_samples.restype = C.c_int
         lib.bling_debug_scene_info.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
         lib.bling_debug_scene_info.restype = C.c_int
         if hasattr(lib, "bling_debug_mis_culled"):    # older experiment builds lack it

@@ -209,6 +209,15 @@ struct LiState {
   size_t chunk = 0;
 };
 
+// The sampler and camera seam (cam_samples.hip): the call's window records (32 B each, cam_samples.h CamWin)
+// and offsets on the device, and the host variant's staging buffers.
+struct CamState {
+  DBuf<uint4> wins;
+  DBuf<unsigned long long> first;
+  DBuf<float> xy, rays, lens;
+  DBuf<uint32_t> ids;
+};
+
 }  // namespace bcore
 
 struct bling_ctx;
@@ -372,6 +381,7 @@ struct bling_ctx {
   MergeState merge;                // the ordered splat merge (splat_merge.h)
   ImageState image;                // the image API (image_ops.hip)
   LiState li;                      // the integrator seam for a caller's rays (li_rays.hip)
+  CamState cam;                    // the sampler and camera seam (cam_samples.hip)
 
   ~bling_ctx() {
     peers.clear();                          // each peer frees its memory on its own device

@@ -11,6 +11,8 @@
 // --film ordered (sampler scenes; the environment's BLING_FILM_ORDERED=1 means the same) forms every pass's film in
 // the reference's order without float atomics (BLING_PASS_ORDERED_FILM): the same files on every run.  The splat
 // renderers refuse it: their switch is --splat.
+// --seams (with --film ordered, sampler scenes, not the bidir integrator) renders each pass as a caller of the seams
+// would: windows -> bling_camera_samples_device -> bling_surface_li_device -> bling_image_add_windowed_device.  Same files.
 //   bling --image-filters [--out DIR] [--size WxH] [--develop host|device] [--device D] [--windows N]
 // reproduces the reference's live command line (main = imageFilters, src/cmdline/Examples.hs:10-58) and is the whole
 // run: for box, gauss 3 3 2, mitchell 3 3 1/3 1/3, sinc 3 3 3 and triangle 3 3 it writes DIR/filter-show-<name>.png
@@ -299,7 +301,7 @@ int image_filters(int argc, char** argv) {
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    std::fprintf(stderr, "usage: %s scene.bling [--overrides S] [--passes N] [--out prefix] [--device D] [--develop host|device] [--splat atomic|ordered] [--film atomic|ordered]\n"
+    std::fprintf(stderr, "usage: %s scene.bling [--overrides S] [--passes N] [--out prefix] [--device D] [--develop host|device] [--splat atomic|ordered] [--film atomic|ordered] [--seams]\n"
                          "       %s --image-filters [--out DIR] [--size WxH] [--develop host|device] [--device D] [--windows N]\n", argv[0], argv[0]);
     return 2;
   }
@@ -311,7 +313,10 @@ int main(int argc, char** argv) {
   bool dev_develop = false, ordered = false;
   const char* film_env = std::getenv("BLING_FILM_ORDERED");
   bool film_ordered = film_env && film_env[0] == '1';
-  for (int i = 2; i + 1 < argc; i += 2) {
+  bool seams = false;
+  for (int i = 2; i < argc; i += 2) {
+    if (!std::strcmp(argv[i], "--seams")) { seams = true; --i; continue; }   // the one switch without a value
+    if (i + 1 >= argc) break;
     if (!std::strcmp(argv[i], "--overrides")) ov = argv[i + 1];
     else if (!std::strcmp(argv[i], "--passes")) passes = std::atoi(argv[i + 1]);
     else if (!std::strcmp(argv[i], "--out")) out = argv[i + 1];
@@ -349,6 +354,14 @@ int main(int argc, char** argv) {
   std::vector<float> film((size_t)w * h * 4, 0.f), rgb((size_t)w * h * 3);
   const bool splats = d->config.renderer == BLING_RENDERER_LIGHT || d->config.renderer == BLING_RENDERER_METROPOLIS ||
                       d->config.renderer == BLING_RENDERER_SPPM;
+  if (seams) {
+    const char* why = splats ? "--seams renders a sampler scene through its seams; this scene's renderer splats"
+                      : d->config.integrator == BLING_INTEGRATOR_BIDIR
+                          ? "--seams: surface_li refuses the bidir integrator (its walk makes the camera ray inside)"
+                      : !film_ordered ? "--seams needs --film ordered: the chain of seams is the ordered film"
+                                      : nullptr;
+    if (why) { std::fprintf(stderr, "%s\n", why); return 2; }
+  }
   if (splats && film_ordered) {
     std::fprintf(stderr, "--film ordered is for sampler scenes; this scene's renderer splats: use --splat ordered\n");
     return 2;
@@ -428,6 +441,60 @@ int main(int argc, char** argv) {
       }
       if ((device_film ? write_pass_device_film(ctx, dev_develop, df, name, film.data(), sw, w, h, rgb)
                        : write_pass(ctx, dev_develop, name, film.data(), splat.data(), sw, w, h, rgb)) != 0) return 1;
+    }
+    bling_destroy(ctx);
+    bling_host_free(hs);
+    return 0;
+  }
+  if (seams) {
+    // prender (Rendering.hs:118-134) written by a caller: splitWindow's 16 x 16 windows of the sample extent, their
+    // samples and rays from the sampler and camera seam, surfaceLi along them, the windows' tiles onto the film --
+    // three device calls a pass; only the windows go up, only the film comes back to be written.
+    bling_image_desc idesc{w, h, d->filter};
+    int32_t e[4];
+    bling_host_image_extent(&idesc, e);
+    std::vector<bling_image_window> wins;
+    std::vector<uint64_t> first(1, 0);
+    for (int wy = e[2]; wy <= e[3]; wy += 16)
+      for (int wx = e[0]; wx <= e[1]; wx += 16) {
+        const bling_image_window wn{wx, std::min(wx + 15, e[1]), wy, std::min(wy + 15, e[3])};
+        wins.push_back(wn);
+        first.push_back(first.back() + (uint64_t)(wn.x1 - wn.x0 + 1) * (uint64_t)(wn.y1 - wn.y0 + 1) * (uint64_t)d->config.spp);
+      }
+    const size_t n = first.back();
+    struct Bufs {
+      void *xy = nullptr, *ids = nullptr, *rays = nullptr, *L = nullptr, *film = nullptr;
+      ~Bufs() { (void)hipFree(xy); (void)hipFree(ids); (void)hipFree(rays); (void)hipFree(L); (void)hipFree(film); }
+    } b;
+    if (hipSetDevice(device) != hipSuccess || hipMalloc(&b.xy, n * 8) != hipSuccess || hipMalloc(&b.ids, n * 8) != hipSuccess ||
+        hipMalloc(&b.rays, n * 28) != hipSuccess || hipMalloc(&b.L, n * 64) != hipSuccess ||
+        hipMalloc(&b.film, film.size() * sizeof(float)) != hipSuccess || hipMemset(b.film, 0, film.size() * sizeof(float)) != hipSuccess) {
+      std::fprintf(stderr, "--seams: %s\n", hipGetErrorString(hipGetLastError()));
+      return 1;
+    }
+    for (int p = 1; p <= passes; ++p) {
+      bling_camera_stats cs;
+      bling_li_stats ls;
+      bling_image_stats is;
+      if (bling_camera_samples_device(ctx, 0x0B11A6u, (uint32_t)p, wins.data(), first.data(), wins.size(), b.xy, b.ids, b.rays, nullptr, &cs) != 0 ||
+          bling_surface_li_device(ctx, 0x0B11A6u, (uint32_t)p, b.rays, b.ids, n, b.L, &ls) != 0 ||
+          bling_image_add_windowed_device(ctx, &idesc, BLING_IMAGE_ADD, wins.data(), first.data(), wins.size(), b.xy, b.L, n, b.film,
+                                          nullptr, &is) != 0) {
+        std::fprintf(stderr, "%s\n", bling_last_error());
+        return 1;
+      }
+      const uint64_t rays = ls.rays + ls.rays_continuation + ls.rays_mis + ls.rays_shadow;
+      const double ms = cs.ms_total + ls.ms_total + is.ms;
+      std::printf("pass %d: %.1f ms (camera %.2f, surface_li %.1f, film %.1f), %llu samples, %.1f Mrays/s\n", p, ms, cs.ms_total,
+                  ls.ms_total, is.ms, (unsigned long long)cs.samples, rays / (ms * 1e3));
+      if (hipMemcpy(film.data(), b.film, film.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+        std::fprintf(stderr, "film: copy failed\n");
+        return 1;
+      }
+      char name[512];
+      std::snprintf(name, sizeof name, "%s-%05d", out, p);
+      std::printf("Writing %s...\n", name);
+      if (write_pass(ctx, dev_develop, name, film.data(), nullptr, 0.f, w, h, rgb) != 0) return 1;
     }
     bling_destroy(ctx);
     bling_host_free(hs);

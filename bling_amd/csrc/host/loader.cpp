@@ -27,6 +27,7 @@
 #include "../common/cr_math.h"
 #include "../common/gamma_table.h"
 #include "../common/image_sample.h"
+#include "camera_samples.h"
 #include "hmath.h"
 #include "image_io.h"
 
@@ -1676,6 +1677,23 @@ int bling_host_image_scale_splats(const bling_image_desc* d, float* splat, const
     const float s = factors ? factors[i] : scalar;
     splat[3 * i] = splat[3 * i] * s; splat[3 * i + 1] = splat[3 * i + 1] * s; splat[3 * i + 2] = splat[3 * i + 2] * s;
   }
+  return 0;
+}
+
+int bling_host_camera_samples(const bling_scene_desc* d, uint32_t seed, uint32_t pass_index, const bling_image_window* windows,
+                              const uint64_t* first, size_t n_windows, float* xy, uint32_t* ids, float* rays_soa, float* lens) {
+  if (!d) { g_err = "camera_samples: null argument"; return -1; }
+  if (!bcam::check(d->config, bcam::sample_extent(*d), windows, first, n_windows, &g_err)) return -1;
+  const uint64_t n = first[n_windows];
+  // no output may alias another: xy, ids and lens hold 8 n bytes, the ray planes 28 n
+  const void* out[4] = {xy, ids, rays_soa, lens};
+  const uint64_t bytes[4] = {8 * n, 8 * n, 28 * n, 8 * n};
+  for (int a = 0; a < 4; ++a)
+    for (int b = a + 1; b < 4; ++b) {
+      const uintptr_t pa = (uintptr_t)out[a], pb = (uintptr_t)out[b];
+      if (n && pa && pb && pa < pb + bytes[b] && pb < pa + bytes[a]) { g_err = "camera_samples: two outputs overlap"; return -1; }
+    }
+  bhcam::run(*d, seed, pass_index, windows, first, n_windows, xy, ids, rays_soa, lens);
   return 0;
 }
 

@@ -56,6 +56,57 @@ def mlt_boot(values, seed, pass_index, chains):
     return np.float32(b[0]), starts
 
 
+CAMERA_OUTPUTS = ("xy", "ids", "rays", "lens")
+
+
+def camera_windows(windows, spp, counts_or_first=None):
+    """The ctypes window array, the n_windows + 1 ascending uint64 offsets and the number of windows of a list of
+    SampleWindows (x0, x1, y0, y1), ends inclusive.  counts_or_first: the windows' sample counts or the offsets;
+    None derives them from the windows and spp -- (x1-x0+1) (y1-y0+1) spp, 0 for an empty window."""
+    wl = [tuple(int(v) for v in w) for w in windows]
+    if any(len(w) != 4 for w in wl):
+        raise ValueError("a window is (x0, x1, y0, y1)")
+    if counts_or_first is None:
+        c = np.asarray([max(0, x1 - x0 + 1) * max(0, y1 - y0 + 1) * int(spp) for x0, x1, y0, y1 in wl], np.int64)
+    else:
+        c = np.asarray(counts_or_first, np.int64).reshape(-1)
+    if len(c) == len(wl):
+        first = np.concatenate([np.zeros(1, np.int64), np.cumsum(c)])
+    elif len(c) == len(wl) + 1:
+        first = c
+    else:
+        raise ValueError(f"{len(wl)} windows need {len(wl)} counts or {len(wl) + 1} offsets, not {len(c)}")
+    arr = (_ffi.ImageWindow * max(1, len(wl)))(*(_ffi.ImageWindow(*w) for w in wl))
+    return arr, np.ascontiguousarray(first.astype(np.uint64)), len(wl)
+
+
+def host_camera_samples(job: Job, windows, seed=DEFAULT_SEED, pass_index=0, counts_or_first=None, outputs=CAMERA_OUTPUTS,
+                        into=None):
+    """bling_host_camera_samples: the samples and camera rays of the SampleWindows on the CPU, through
+    libbling_host -- no context, no GPU.  Returns (xy (n, 2) float32, ids (n, 2) uint32, rays (7, n) float32,
+    lens (n, 2) float32) as numpy arrays; one not named in outputs is None.  into: a dict of preallocated arrays
+    to write into instead.  ValueError where the library refuses (nothing is written then)."""
+    arr, first, nw = camera_windows(windows, job.spp, counts_or_first)
+    n = int(first[-1])
+    shapes = {"xy": ((n, 2), np.float32), "ids": ((n, 2), np.uint32), "rays": ((7, n), np.float32), "lens": ((n, 2), np.float32)}
+    bufs = {}
+    for k in CAMERA_OUTPUTS:
+        if k not in outputs:
+            bufs[k] = None
+        elif into is not None and k in into:
+            bufs[k] = into[k]
+        else:
+            bufs[k] = np.zeros(*shapes[k])
+    ptr = {k: (None if b is None else C.c_void_p(b.ctypes.data)) for k, b in bufs.items()}
+    lib = _ffi.host()
+    rc = lib.bling_host_camera_samples(C.c_void_p(job.desc), seed, pass_index, arr, first.ctypes.data_as(C.POINTER(C.c_uint64)), nw,
+                                       C.cast(ptr["xy"], _ffi.c_f32p), C.cast(ptr["ids"], _ffi.c_u32p),
+                                       C.cast(ptr["rays"], _ffi.c_f32p), C.cast(ptr["lens"], _ffi.c_f32p))
+    if rc != 0:
+        raise ValueError(lib.bling_host_last_error().decode())
+    return bufs["xy"], bufs["ids"], bufs["rays"], bufs["lens"]
+
+
 class Context:
     """One bling_ctx (bling_create / bling_destroy) on one HIP device, or on several: a list of
     device ids makes every render pass fan out over all of them inside the library (include/bling.h,
@@ -401,6 +452,66 @@ class Context:
         _check(_ffi.hip().bling_surface_li(self._h, seed, pass_index, _ffi.f32ptr(rays) if n else None,
                                            _ffi.u32ptr(ids) if n else None, n, _ffi.f32ptr(L) if n else None, C.byref(st)))
         return L, st
+
+    def camera_samples(self, windows, seed=DEFAULT_SEED, pass_index=0, counts_or_first=None, out=None):
+        """bling_camera_samples_device: the uploaded scene's sampler and camera over the SampleWindows
+        (x0, x1, y0, y1), ends inclusive -- window k's pixels y outer, x inner, n innermost in slots
+        first[k] .. first[k+1]-1.  counts_or_first: the windows' sample counts or the n_windows + 1 offsets; None
+        derives them from the windows and the job's spp.  Returns (xy, ids, rays, lens, CameraStats) as torch
+        tensors on this context's first device: xy (n, 2) float32 as Image.add_windowed takes it, ids (n, 2) int32
+        and rays (7, n) float32 as surface_li takes them, lens (n, 2) float32.  out: a dict naming some of "xy",
+        "ids", "rays", "lens" -- a tensor to write into, or False to leave that output out (it is returned as
+        None); outputs not named are allocated.  Only the windows and offsets go from the host to the device.
+        The call runs on the context's own stream and returns after completion."""
+        import torch
+        if self.job is None:
+            raise BlingError(-4, "no scene uploaded")
+        dev = f"cuda:{self.device}"
+        arr, first, nw = camera_windows(windows, self.job.spp, counts_or_first)
+        n = int(first[-1])
+        shapes = {"xy": ((n, 2), torch.float32), "ids": ((n, 2), torch.int32), "rays": ((7, n), torch.float32),
+                  "lens": ((n, 2), torch.float32)}
+        out = dict(out or {})
+        if set(out) - set(CAMERA_OUTPUTS):
+            raise ValueError(f"camera_samples: out names {sorted(set(out) - set(CAMERA_OUTPUTS))}, not among {CAMERA_OUTPUTS}")
+        bufs = {}
+        for k, (shape, dt) in shapes.items():
+            t = out.get(k)
+            if t is False:
+                bufs[k] = None
+            elif t is None:
+                bufs[k] = torch.empty(shape, dtype=dt, device=dev)
+            else:
+                types = (dt, torch.uint32) if k == "ids" and hasattr(torch, "uint32") else (dt,)
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.device and t.dtype in types
+                        and t.is_contiguous() and t.numel() == shape[0] * shape[1]):
+                    raise ValueError(f"camera_samples: out[{k!r}] must be a contiguous {dt} tensor of {shape[0] * shape[1]} elements on {dev}")
+                bufs[k] = t
+        torch.cuda.synchronize(self.device)
+        st = _ffi.CameraStats()
+        ptr = [C.c_void_p(bufs[k].data_ptr() if bufs[k] is not None and n else None) for k in CAMERA_OUTPUTS]
+        _check(_ffi.hip().bling_camera_samples_device(self._h, seed, pass_index, arr, first.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                      nw, *ptr, C.byref(st)))
+        return bufs["xy"], bufs["ids"], bufs["rays"], bufs["lens"], st
+
+    def host_camera_samples(self, windows, seed=DEFAULT_SEED, pass_index=0, counts_or_first=None, outputs=CAMERA_OUTPUTS):
+        """bling_host_camera_samples of the uploaded job: camera_samples on the CPU through libbling_host, as numpy
+        arrays (xy, ids, rays, lens); see the module's host_camera_samples, which needs no context."""
+        if self.job is None:
+            raise BlingError(-4, "no scene uploaded")
+        return host_camera_samples(self.job, windows, seed, pass_index, counts_or_first, outputs)
+
+    def render_pass_by_seams(self, image, windows, seed=DEFAULT_SEED, pass_index=0):
+        """One sampler-renderer pass as three device calls: camera_samples -> surface_li -> image.add_windowed
+        (a bling_amd.image.Image that shares this context).  With splitWindow's windows of the extent the film
+        equals render_pass(ordered=True)'s bit for bit.  Returns (CameraStats, LiStats, ImageStats)."""
+        if self.job is None:
+            raise BlingError(-4, "no scene uploaded")
+        _, first, _ = camera_windows(windows, self.job.spp)
+        xy, ids, rays, _, cst = self.camera_samples(windows, seed, pass_index, first, out={"lens": False})
+        L, lst = self.surface_li(rays, ids, seed, pass_index)
+        ist = image.add_windowed(windows, first, xy, L, "add")
+        return cst, lst, ist
 
     def set_li_chunk(self, max_rays=0):
         """bling_debug_set_li_chunk: the rays per wave of surface_li / host_surface_li (0: the default)."""

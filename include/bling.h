@@ -680,6 +680,53 @@ int bling_surface_li(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, const f
 /* Test hook: the rays per wave of this context's bling_surface_li* calls; 0 restores the default. */
 int bling_debug_set_li_chunk(bling_ctx* ctx, size_t max_rays);
 
+/* ---- the sampler and camera seam: a window's samples and rays, on device buffers ----
+ * Replaces: the first third of prender's per-window work (Rendering.hs:118-134): `sample sampler window`
+ * (Sampling.hs:101-132) walking the window's pixels, and fireRay cam (Camera.hs:49-76) of every sample -- for a
+ * caller that keeps its own loop and wants the built-in sampler's and camera's samples but its own treatment of
+ * them.  The outputs are what the other seams take: windows -> bling_camera_samples_device ->
+ * bling_surface_li_device -> bling_image_add_windowed_device -> develop is a sampler-renderer pass whose film
+ * equals the ordered film of bling_render_pass bit for bit, and the host sends only the windows.
+ *   windows: n_windows SampleWindows (host array, ends inclusive, as the image calls take it); x1 < x0 or
+ *     y1 < y0 is an empty window.
+ *   first: n_windows + 1 ascending sample offsets (host array) from 0, the image calls' convention: window k owns
+ *     slots first[k] .. first[k+1]-1, its pixels y outer, x inner, n = 0 .. spp-1 innermost (coverWindow's
+ *     order); first[k+1] - first[k] must equal (x1-x0+1) (y1-y0+1) spp, 0 for an empty window.
+ *     n = first[n_windows].
+ *   xy_dev: 2 n floats, imageX, imageY: the xy of bling_image_add_*_device.
+ *   ids_dev: 2 n uint32, (pixel, n) with pixel = (iy - ey0) * ext_w + (ix - ex0): the ids of
+ *     bling_surface_li_device.
+ *   rays_soa_dev: 7 planes of n floats, ox oy oz dx dy dz tmin of fireRay, tmin = 0: its rays_soa.
+ *   lens_dev: 2 n floats, the lens sample (lu, lv), for a caller that applies its own lens.
+ *   Each of the four may be NULL and is then not produced; the others' bits do not depend on that.
+ * A window's block depends on the window, the seed, the pass and the uploaded scene only: not on the other
+ * windows, their order, or how the call is cut (two calls over halves of the list, into offset pointers, give
+ * the bits of one).  Windows may overlap, nest, repeat or be empty.  Every integrator of the sampler renderer
+ * is served, `bidir` included: the camera sample does not depend on the integrator.  The outputs equal
+ * bling_host_camera_samples (bling_host.h) of the same description bit for bit.  No path state of the context
+ * is touched.  Any n is served with 64-bit slot arithmetic; a call of more than 2^30 samples is cut into
+ * launches.
+ * Errors: BLING_EINVAL for a NULL ctx; BLING_ENOSCENE without a scene; then BLING_EINVAL, with nothing written,
+ * for a scene whose renderer is not `sampler`, a NULL first (or windows, when n_windows > 0), a first that does
+ * not start at 0 or does not match the windows' counts, a non-empty window with a pixel outside the scene's
+ * sample extent (the stream id is defined inside the extent only), an output that is not aligned to 4 bytes or
+ * that overlaps another.  n = 0 succeeds.  stats may be NULL.
+ * bling_camera_samples_device: the four outputs are device buffers on device_ids[0] (e.g. torch tensors'
+ *   data_ptr()).  The call runs on the context's stream and returns after completion; a multi-device context
+ *   runs it on device_ids[0], as bling_surface_li_device.
+ * bling_camera_samples: the four are host buffers, staged through device buffers the context owns. */
+typedef struct bling_camera_stats {
+    uint64_t samples;           /* n                                                                */
+    uint64_t windows;           /* n_windows                                                        */
+    double   ms_total;          /* device time of the call (one pair of HIP events)                 */
+} bling_camera_stats;
+int bling_camera_samples_device(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, const bling_image_window* windows,
+                                const uint64_t* first, size_t n_windows, void* xy_dev, void* ids_dev, void* rays_soa_dev,
+                                void* lens_dev, bling_camera_stats* stats);
+int bling_camera_samples(bling_ctx* ctx, uint32_t seed, uint32_t pass_index, const bling_image_window* windows,
+                         const uint64_t* first, size_t n_windows, float* xy, uint32_t* ids, float* rays_soa, float* lens,
+                         bling_camera_stats* stats);
+
 /* Diagnostics (no reference counterpart): the path-state bytes the shading kernel k_shade moved in
  * the context's last bling_render_pass*, per stream and direction -- out[2 k] read, out[2 k + 1]
  * written, stream k in the order BLING_STREAM_NAMES lists -- counted where the algorithm needs

@@ -132,6 +132,25 @@ int   bling_host_image_add_windowed(const bling_image_desc* desc, int op, const 
  * s = factors[i] of pixel i, or scalar when factors is NULL.  splitMImage (Image.hs:84-91) is a zeroed image of
  * the same shape and needs no call. */
 int   bling_host_image_scale_splats(const bling_image_desc* desc, float* splat, const float* factors, float scalar);
+/* ---- the host side of the sampler and camera seam (bling_camera_samples*, bling.h) ----
+ * The samples and camera rays of SampleWindows, on the CPU: `sample sampler window` (Sampling.hs:101-132, the
+ * counter RNG of DESIGN.md in place of MWC) walks a window's pixels y outer, x inner, n = 0 .. spp-1 innermost
+ * (coverWindow's order), and every sample fires fireRay (Camera.hs:49-76) of the description's camera.  It needs
+ * no context and no GPU: the sequential yardstick of bling_camera_samples_device, whose outputs equal these bit
+ * for bit, and the path for a host without a device.  Binary32 in the operation order of the device's
+ * camera_sample / fire_ray, compiled without multiply-add contraction.
+ *   windows: n_windows SampleWindows, ends inclusive; x1 < x0 or y1 < y0 is an empty window.
+ *   first: n_windows + 1 ascending offsets from 0; first[k+1] - first[k] must be (x1-x0+1) (y1-y0+1) spp of
+ *     window k (0 for an empty one).  n = first[n_windows].
+ *   xy: 2 n floats (imageX, imageY); ids: 2 n uint32 (pixel, n), pixel = (iy - ey0) * ext_w + (ix - ex0) over
+ *     the sample extent; rays_soa: 7 planes of n floats, ox oy oz dx dy dz tmin (tmin = 0); lens: 2 n floats,
+ *     the lens sample (lu, lv).  Any of the four may be NULL.
+ * A window's block depends on the window, the seed, the pass and the description only.  0, or -1 with nothing
+ * written: a NULL desc or first, a renderer block that is not the sampler renderer's, a first that does not match
+ * the counts, a non-empty window with a pixel outside the sample extent, two outputs that overlap. */
+int   bling_host_camera_samples(const bling_scene_desc* desc, uint32_t seed, uint32_t pass_index,
+                                const bling_image_window* windows, const uint64_t* first, size_t n_windows, float* xy,
+                                uint32_t* ids, float* rays_soa, float* lens);
 /* rgbToSpectrumIllum (Spectrum.hs:146-159 over the illuminant bases), as the loader applies it to image maps. */
 void  bling_host_rgb_to_spectrum_illum(const float rgb[3], float out16[16]);
 
