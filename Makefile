@@ -21,12 +21,12 @@ ORADIR   := oracle/_build
 LTRDIR   := tests/ref/_build
 space    := $(subst ,, )
 
-HOST_SRC := bling_amd/csrc/host/loader.cpp
+HOST_SRC := bling_amd/csrc/host/loader.cpp bling_amd/csrc/host/lbvh_host.cpp
 HOST_HDR := bling_amd/csrc/host/hmath.h bling_amd/csrc/common/sky_model.h bling_amd/csrc/common/scene_features.h \
             bling_amd/csrc/common/spectral_data.h bling_amd/csrc/common/perlin.h include/bling_scene.h include/bling_host.h \
             bling_amd/csrc/common/image_tex.h bling_amd/csrc/common/cr_math.h bling_amd/csrc/host/image_io.h \
             bling_amd/csrc/common/gamma_table.h bling_amd/csrc/common/image_sample.h bling_amd/csrc/host/camera_samples.h \
-            bling_amd/csrc/common/cam_windows.h bling_amd/csrc/common/counter_rng.h
+            bling_amd/csrc/common/cam_windows.h bling_amd/csrc/common/counter_rng.h bling_amd/csrc/common/lbvh.h
 CORE_SRC := $(wildcard bling_amd/csrc/core/*.hip) $(wildcard bling_amd/csrc/core/*.cpp)
 # STUB (experiment builds only) is part of the object directory: stubbed units never mix with real ones
 ifneq ($(strip $(STUB)),)
@@ -40,7 +40,8 @@ CORE_HDR := $(wildcard bling_amd/csrc/core/*.h) bling_amd/csrc/common/sky_model.
             bling_amd/csrc/common/spectral_data.h bling_amd/csrc/common/counter_rng.h include/bling.h include/bling_scene.h \
             bling_amd/csrc/common/scene_features.h bling_amd/csrc/common/perlin.h bling_amd/csrc/common/cr_math.h \
             bling_amd/csrc/common/fast_cr.h bling_amd/csrc/common/cellnoise.h bling_amd/csrc/common/image_tex.h \
-            bling_amd/csrc/common/gamma_table.h bling_amd/csrc/common/image_sample.h bling_amd/csrc/common/cam_windows.h
+            bling_amd/csrc/common/gamma_table.h bling_amd/csrc/common/image_sample.h bling_amd/csrc/common/cam_windows.h \
+            bling_amd/csrc/common/lbvh.h
 REF_HDR  := $(wildcard tests/ref/*.h)
 ORA_SRC  := $(wildcard oracle/*.cpp)
 ORA_HDR  := $(wildcard oracle/*.h) include/bling_scene.h bling_amd/csrc/common/perlin.h bling_amd/csrc/common/cr_math.h \

@@ -174,6 +174,28 @@ class CameraStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+BVH_BUILDERS = {"host": 0, "device": 1}                                          # BLING_BVH_*
+BVH_FALLBACKS = ["none", "fractal", "items", "depth", "refs"]                    # BLING_BVH_FALLBACK_*
+
+
+class UploadParams(C.Structure):
+    """bling_upload_params (include/bling.h)."""
+    _fields_ = [("bvh_builder", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class BvhBuildInfo(C.Structure):
+    """bling_bvh_build_info (include/bling.h)."""
+    _fields_ = [("requested", C.c_uint32), ("used", C.c_uint32), ("fallback", C.c_uint32), ("items", C.c_uint32),
+                ("nodes", C.c_uint32), ("depth", C.c_uint32), ("leaves", C.c_uint32), ("max_leaf", C.c_uint32),
+                ("ms_build", C.c_double), ("ms_derive", C.c_double)]
+
+
+class LbvhInfo(C.Structure):
+    """bling_lbvh_info (include/bling_host.h)."""
+    _fields_ = [("items", C.c_uint32), ("nodes", C.c_uint32), ("depth", C.c_uint32), ("leaves", C.c_uint32),
+                ("max_leaf", C.c_uint32)]
+
+
 class RenderConfig(C.Structure):
     _fields_ = [("renderer", C.c_int32), ("sampler", C.c_int32), ("nu", C.c_int32), ("nv", C.c_int32),
                 ("spp", C.c_int32), ("max_depth", C.c_int32), ("sample_depth", C.c_int32),
@@ -244,6 +266,9 @@ def host() -> C.CDLL:
         lib.bling_host_camera_samples.restype = C.c_int
         lib.bling_host_rgb_to_spectrum_illum.argtypes = [c_f32p, c_f32p]
         lib.bling_host_rgb_to_spectrum_illum.restype = None
+        lib.bling_host_lbvh.argtypes = [c_f32p, c_u32p, C.c_size_t, C.c_int, c_f32p, c_u32p, C.POINTER(C.c_uint64),
+                                        C.POINTER(LbvhInfo)]
+        lib.bling_host_lbvh.restype = C.c_int
         _host = lib
     return _host
 
@@ -257,6 +282,7 @@ HIP_SYMBOLS = ["bling_create", "bling_scene_upload", "bling_scene_validate", "bl
                "bling_image_add_windowed_device", "bling_image_add_windowed", "bling_image_scale_splats_device",
                "bling_surface_li_device", "bling_surface_li", "bling_debug_set_li_chunk",
                "bling_camera_samples_device", "bling_camera_samples",
+               "bling_scene_upload_with", "bling_debug_bvh", "bling_debug_bvh_build_info", "bling_debug_set_bvh_depth_cap",
                "bling_destroy", "bling_last_error", "bling_version"]
 
 
@@ -423,6 +449,16 @@ def hip() -> C.CDLL:
             lib.bling_debug_stream_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t,
                                                      C.POINTER(C.c_size_t)]
             lib.bling_debug_stream_bytes.restype = C.c_int
+        if hasattr(lib, "bling_scene_upload_with"):   # older experiment builds lack the device BVH builder
+            lib.bling_scene_upload_with.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(UploadParams)]
+            lib.bling_scene_upload_with.restype = C.c_int
+            lib.bling_debug_bvh.argtypes = [C.c_void_p, c_f32p, C.c_size_t, c_u32p, C.c_size_t, C.POINTER(C.c_size_t),
+                                            C.POINTER(C.c_size_t)]
+            lib.bling_debug_bvh.restype = C.c_int
+            lib.bling_debug_bvh_build_info.argtypes = [C.c_void_p, C.POINTER(BvhBuildInfo)]
+            lib.bling_debug_bvh_build_info.restype = C.c_int
+            lib.bling_debug_set_bvh_depth_cap.argtypes = [C.c_void_p, C.c_int]
+            lib.bling_debug_set_bvh_depth_cap.restype = C.c_int
         lib.bling_destroy.argtypes = [C.c_void_p]
         lib.bling_last_error.restype = C.c_char_p
         lib.bling_version.restype = C.c_char_p

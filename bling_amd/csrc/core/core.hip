@@ -220,7 +220,43 @@ __global__ void k_tri_frames(const float* __restrict__ pts, const float* __restr
   if (t < n) tri_frame_build(pts + (size_t)9 * t, uvs + (size_t)6 * t, out + (size_t)4 * t);
 }
 
-void upload_scene(bling_ctx* c, const bling_scene_desc* d) {
+double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// The BVH2 of the items by the builder asked for (BLING_BVH_*), and how it came about.  The device builder
+// (bvh_device.hip) stands down for what bling.h lists; the host's binned SAH then builds as it always did.
+bvh::Result build_bvh2(bling_ctx* c, const std::vector<bvh::Box>& boxes, const std::vector<uint32_t>& refs, bool fractal,
+                       uint32_t builder, bling_bvh_build_info* info) {
+  *info = bling_bvh_build_info{};
+  info->requested = info->used = builder;
+  info->items = (uint32_t)boxes.size();
+  bvh::Result R;
+  if (builder == BLING_BVH_DEVICE) {
+    const int cap = c->bvh_depth_cap ? c->bvh_depth_cap : STACK_DEPTH - 1;
+    if (fractal) info->fallback = BLING_BVH_FALLBACK_FRACTAL;
+    else if (boxes.size() < 3) info->fallback = BLING_BVH_FALLBACK_ITEMS;
+    else if (boxes.size() > ((size_t)1 << 24)) info->fallback = BLING_BVH_FALLBACK_REFS;
+    else {
+      float ms = 0.f;
+      int depth = 0;
+      if (lbvh_build_device(c, boxes, refs, cap, R, &ms, &depth)) { info->ms_build = ms; return R; }
+      info->fallback = BLING_BVH_FALLBACK_DEPTH;
+    }
+    info->used = BLING_BVH_HOST;
+  }
+  // Leaves of at most two primitives: the all-LDS BVH4 kernel tests two primitives per step, so a
+  // leaf costs one step (A/B, profiles/r02_ab_bvh_leaf_s5.txt: C2 closest-hit 37.4 -> 31.5 ms per
+  // pass against leaves of up to 4; C3, C4 and C5 within noise).
+  const auto t0 = std::chrono::steady_clock::now();
+  R = bvh::build(boxes, refs, 2);
+  info->ms_build = ms_since(t0);
+  return R;
+}
+
+// given: the BVH2 another context of the fan-out built for this scene (peers), or nullptr to build it here
+// with `builder`; keep (may be nullptr) receives a copy of the tree built here.
+void upload_scene(bling_ctx* c, const bling_scene_desc* d, uint32_t builder, const bvh::Result* given, bvh::Result* keep) {
   HIPCHK(hipSetDevice(c->device));
   DevScene& S = c->S;
   S = DevScene{};
@@ -316,10 +352,10 @@ void upload_scene(bling_ctx* c, const bling_scene_desc* d) {
     S.world_r = sqrtf(dd[0] * dd[0] + dd[1] * dd[1] + dd[2] * dd[2]);
     for (int a = 0; a < 3; ++a) { S.kd_lo[a] = lo[a]; S.kd_hi[a] = hi[a]; }
   }
-  // Leaves of at most two primitives: the all-LDS BVH4 kernel tests two primitives per step, so a
-  // leaf costs one step (A/B, profiles/r02_ab_bvh_leaf_s5.txt: C2 closest-hit 37.4 -> 31.5 ms per
-  // pass against leaves of up to 4; C3, C4 and C5 within noise).
-  bvh::Result R = bvh::build(boxes, refs, 2);
+  bling_bvh_build_info info{};
+  const bvh::Result R = given ? *given : build_bvh2(c, boxes, refs, fractal_prim >= 0, builder, &info);
+  if (keep) *keep = R;
+  const auto t_derive = std::chrono::steady_clock::now();
   c->nodes.upload(reinterpret_cast<const float4*>(R.nodes.data()), R.nodes.size() / 4);
   c->refs.upload(R.refs.data(), R.refs.size());
   {
@@ -388,6 +424,12 @@ void upload_scene(bling_ctx* c, const bling_scene_desc* d) {
     const bool on = fractal_prim < 0 && nt + ns > 0 && nt + ns <= lim && R.refs.size() == (size_t)nt + ns;
     S.bf_tris = on ? nt : 0u;
     S.bf_shapes = on ? ns : 0u;
+  }
+  if (!given) {
+    info.nodes = (uint32_t)(R.nodes.size() / 16);
+    info.depth = (uint32_t)R.depth; info.leaves = (uint32_t)R.leaves; info.max_leaf = (uint32_t)R.max_leaf;
+    info.ms_derive = ms_since(t_derive);
+    c->bvh_info = info;
   }
   c->tri_prim.upload(tri_prim.data(), nt);
   c->shape_prim.upload(shape_prim.data(), ns);
@@ -993,21 +1035,61 @@ int bling_create(const int* device_ids, int n_devices, bling_ctx** out) {
   });
 }
 
-int bling_scene_upload(bling_ctx* c, const bling_scene_desc* d) {
+int bling_scene_upload_with(bling_ctx* c, const bling_scene_desc* d, const bling_upload_params* up) {
   return guarded([&] {
-    if (!c || !d) throw std::invalid_argument("null argument");
+    if (!c || !d || !up) throw std::invalid_argument("null argument");
+    if (up->bvh_builder != BLING_BVH_HOST && up->bvh_builder != BLING_BVH_DEVICE) throw std::invalid_argument("unknown BVH builder");
+    if (up->flags != 0u) throw std::invalid_argument("unknown upload flags");
     validate_scene(d);
     // no pass may mix a new scene on one device with an old or half-uploaded one on another: the
     // context and every peer lose their scene first and get it back only once all uploads succeeded
     c->has_scene = false;
     for (auto& q : c->peers) q->has_scene = false;
-    upload_scene(c, d);
-    for (auto& q : c->peers) upload_scene(q.get(), d);   // replicated scene (8e)
+    // the BVH2 is built once, on the first device; the peers derive the same arrays from it
+    bvh::Result R;
+    upload_scene(c, d, up->bvh_builder, nullptr, c->peers.empty() ? nullptr : &R);
+    for (auto& q : c->peers) {                           // replicated scene (8e)
+      upload_scene(q.get(), d, up->bvh_builder, &R, nullptr);
+      q->bvh_info = c->bvh_info;
+    }
     HIPCHK(hipSetDevice(c->device));
     for (auto& q : c->peers) q->has_scene = true;
     c->has_scene = true;
     return BLING_OK;
   });
+}
+
+int bling_scene_upload(bling_ctx* c, const bling_scene_desc* d) {
+  const bling_upload_params up{BLING_BVH_HOST, 0u};
+  return bling_scene_upload_with(c, d, &up);
+}
+
+int bling_debug_bvh(bling_ctx* c, float* nodes, size_t cap_nodes, uint32_t* refs, size_t cap_refs, size_t* n_nodes, size_t* n_refs) {
+  return guarded([&] {
+    if (!c || !n_nodes || !n_refs) throw std::invalid_argument("null argument");
+    if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
+    *n_nodes = c->nodes.n / 4;
+    *n_refs = c->refs.n;
+    if (!nodes && !refs) return BLING_OK;
+    if ((nodes && cap_nodes < *n_nodes) || (refs && cap_refs < *n_refs)) throw std::invalid_argument("capacity below the BVH's size");
+    HIPCHK(hipSetDevice(c->device));
+    if (nodes && c->nodes.n) HIPCHK(hipMemcpy(nodes, c->nodes.p, c->nodes.n * sizeof(float4), hipMemcpyDeviceToHost));
+    if (refs && c->refs.n) HIPCHK(hipMemcpy(refs, c->refs.p, c->refs.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return BLING_OK;
+  });
+}
+
+int bling_debug_bvh_build_info(bling_ctx* c, bling_bvh_build_info* out) {
+  if (!c || !out) { g_err = "null argument"; return BLING_EINVAL; }
+  if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
+  *out = c->bvh_info;
+  return BLING_OK;
+}
+
+int bling_debug_set_bvh_depth_cap(bling_ctx* c, int cap) {
+  if (!c || cap < 0 || cap > STACK_DEPTH - 1) { g_err = "bad argument"; return BLING_EINVAL; }
+  c->bvh_depth_cap = cap;
+  return BLING_OK;
 }
 
 int bling_scene_validate(const bling_scene_desc* d) {

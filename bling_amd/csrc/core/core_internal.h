@@ -255,6 +255,11 @@ void develop_table(bling_ctx* c);
 void develop_launch(bling_ctx* c, const bling_develop_params* dp, const float* film, const float* splat, void* out);
 // the same for an image of w x h pixels that is not the uploaded scene's (bling_image_develop_device)
 void develop_launch(bling_ctx* c, const bling_develop_params* dp, int w, int h, const float* film, const float* splat, void* out);
+// bvh_device.hip: the linear BVH of common/lbvh.h over the items (3 <= n <= 2^24), built on the context's device
+// and read back into R once.  false, with R untouched, when the tree is deeper than depth_cap (*depth holds
+// its depth).  *ms: HIP events around the kernels.
+bool lbvh_build_device(bling_ctx* c, const std::vector<bvh::Box>& boxes, const std::vector<uint32_t>& refs, int depth_cap,
+                       bvh::Result& R, float* ms, int* depth);
 }  // namespace bcore
 
 // the context lives in the global namespace (include/bling.h declares `struct bling_ctx`)
@@ -354,6 +359,8 @@ struct bling_ctx {
   DBuf<uint32_t> tr_prim;
   // bvh stats
   int bvh_depth = 0, bvh_leaves = 0, bvh_max_leaf = 0, bvh4_depth = 0;
+  bling_bvh_build_info bvh_info{};   // how the uploaded BVH2 was built (bling_debug_bvh_build_info)
+  int bvh_depth_cap = 0;             // bling_debug_set_bvh_depth_cap: 0 = STACK_DEPTH - 1
   uint32_t num_prims = 0;
   uint32_t features = FT_ALL;   // scene_features() of the uploaded scene
   size_t lds_trace = 0;         // dynamic LDS bytes of the traversal kernels

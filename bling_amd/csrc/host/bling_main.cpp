@@ -3,7 +3,7 @@
 // pass-NNNNN.png and .hdr at PassDone) over the host loader and the MI355X core.
 //
 //   bling <scene.bling> [--overrides "image=W,H;..."] [--passes N] [--out prefix] [--device D]
-//         [--develop host|device] [--splat atomic|ordered] [--film atomic|ordered]
+//         [--develop host|device] [--splat atomic|ordered] [--film atomic|ordered] [--bvh host|device]
 // --develop device makes each written pass's 8-bit and RGBE pixels on the device (bling_film_develop)
 // and hands them to the encoders; the default, host, develops with the host library.  Same files.
 // --splat ordered (light tracer, Metropolis and SPPM scenes) adds every pixel's splats in the reference's order
@@ -301,7 +301,7 @@ int image_filters(int argc, char** argv) {
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    std::fprintf(stderr, "usage: %s scene.bling [--overrides S] [--passes N] [--out prefix] [--device D] [--develop host|device] [--splat atomic|ordered] [--film atomic|ordered] [--seams]\n"
+    std::fprintf(stderr, "usage: %s scene.bling [--overrides S] [--passes N] [--out prefix] [--device D] [--develop host|device] [--splat atomic|ordered] [--film atomic|ordered] [--seams] [--bvh host|device]\n"
                          "       %s --image-filters [--out DIR] [--size WxH] [--develop host|device] [--device D] [--windows N]\n", argv[0], argv[0]);
     return 2;
   }
@@ -314,6 +314,8 @@ int main(int argc, char** argv) {
   const char* film_env = std::getenv("BLING_FILM_ORDERED");
   bool film_ordered = film_env && film_env[0] == '1';
   bool seams = false;
+  uint32_t bvh_builder = BLING_BVH_HOST;
+  bool bvh_line = false;
   for (int i = 2; i < argc; i += 2) {
     if (!std::strcmp(argv[i], "--seams")) { seams = true; --i; continue; }   // the one switch without a value
     if (i + 1 >= argc) break;
@@ -339,6 +341,13 @@ int main(int argc, char** argv) {
         return 2;
       }
       film_ordered = !std::strcmp(argv[i + 1], "ordered");
+    } else if (!std::strcmp(argv[i], "--bvh")) {
+      if (std::strcmp(argv[i + 1], "host") && std::strcmp(argv[i + 1], "device")) {
+        std::fprintf(stderr, "--bvh takes host or device, not %s\n", argv[i + 1]);
+        return 2;
+      }
+      bvh_builder = !std::strcmp(argv[i + 1], "device") ? BLING_BVH_DEVICE : BLING_BVH_HOST;
+      bvh_line = true;
     }
   }
   bling_host_scene* hs = nullptr;
@@ -346,9 +355,19 @@ int main(int argc, char** argv) {
   std::printf("Job Stats\n   %s\n", bling_host_summary(hs));
   const bling_scene_desc* d = bling_host_desc(hs);
   bling_ctx* ctx = nullptr;
-  if (bling_create(&device, 1, &ctx) != 0 || bling_scene_upload(ctx, d) != 0) {
+  const bling_upload_params up{bvh_builder, 0u};
+  if (bling_create(&device, 1, &ctx) != 0 || bling_scene_upload_with(ctx, d, &up) != 0) {
     std::fprintf(stderr, "%s\n", bling_last_error());
     return 1;
+  }
+  if (bvh_line) {                      // --bvh: how the BVH2 was built
+    bling_bvh_build_info bi;
+    if (bling_debug_bvh_build_info(ctx, &bi) != 0) { std::fprintf(stderr, "%s\n", bling_last_error()); return 1; }
+    static const char* const why[] = {"", " (fractal scene: host tree)", " (fewer than 3 items: host tree)",
+                                      " (deeper than the traversal stack: host tree)", " (too many items: host tree)"};
+    std::printf("bvh: builder %s%s, %u items, %u nodes, depth %u, build %.3f ms, derive %.3f ms\n",
+                bi.used == BLING_BVH_DEVICE ? "device" : "host", why[bi.fallback <= 4 ? bi.fallback : 0], bi.items, bi.nodes,
+                bi.depth, bi.ms_build, bi.ms_derive);
   }
   int w = d->config.width, h = d->config.height;
   std::vector<float> film((size_t)w * h * 4, 0.f), rgb((size_t)w * h * 3);

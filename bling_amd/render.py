@@ -123,10 +123,44 @@ class Context:
         self.devices = ids
         self.job: Job | None = None
 
-    def upload(self, job: Job):
-        """bling_scene_upload (replaces Scene.mkScene -> mkKdTree)."""
-        _check(_ffi.hip().bling_scene_upload(self._h, C.c_void_p(job.desc)))
+    def upload(self, job: Job, bvh: str | int | None = None):
+        """bling_scene_upload (replaces Scene.mkScene -> mkKdTree).  bvh: "host" (the default: the binned SAH
+        on the host) or "device" (the linear BVH built on the device, bling_scene_upload_with); an integer is
+        passed on as the BLING_BVH_* value it is."""
+        if bvh is None:
+            _check(_ffi.hip().bling_scene_upload(self._h, C.c_void_p(job.desc)))
+        else:
+            if isinstance(bvh, str) and bvh not in _ffi.BVH_BUILDERS:
+                raise ValueError(f"bvh is 'host' or 'device', not {bvh!r}")
+            up = _ffi.UploadParams(_ffi.BVH_BUILDERS[bvh] if isinstance(bvh, str) else int(bvh), 0)
+            _check(_ffi.hip().bling_scene_upload_with(self._h, C.c_void_p(job.desc), C.byref(up)))
         self.job = job
+
+    def bvh(self):
+        """bling_debug_bvh: the uploaded BVH2 as (nodes (n, 16) float32, refs (m,) uint32), whichever builder
+        made it.  The links (words 12 and 13 of a node) are int32 bit patterns: nodes.view(np.int32)."""
+        nn, nr = C.c_size_t(), C.c_size_t()
+        _check(_ffi.hip().bling_debug_bvh(self._h, None, 0, None, 0, C.byref(nn), C.byref(nr)))
+        nodes = np.zeros((int(nn.value), 16), np.float32)
+        refs = np.zeros(int(nr.value), np.uint32)
+        _check(_ffi.hip().bling_debug_bvh(self._h, _ffi.f32ptr(nodes), nodes.shape[0], _ffi.u32ptr(refs), len(refs),
+                                          C.byref(nn), C.byref(nr)))
+        return nodes, refs
+
+    def bvh_build_info(self) -> dict:
+        """bling_debug_bvh_build_info: the builder asked for and used ("host" / "device"), the fallback reason
+        ("none", "fractal", "items", "depth", "refs"), items, nodes, depth, leaves, max_leaf, ms_build, ms_derive."""
+        bi = _ffi.BvhBuildInfo()
+        _check(_ffi.hip().bling_debug_bvh_build_info(self._h, C.byref(bi)))
+        names = {v: k for k, v in _ffi.BVH_BUILDERS.items()}
+        out = {k: getattr(bi, k) for k, _ in bi._fields_}
+        out["requested"], out["used"] = names[bi.requested], names[bi.used]
+        out["fallback"] = _ffi.BVH_FALLBACKS[bi.fallback]
+        return out
+
+    def set_bvh_depth_cap(self, cap=0):
+        """bling_debug_set_bvh_depth_cap: the depth above which the device builder stands down (0: 31)."""
+        _check(_ffi.hip().bling_debug_set_bvh_depth_cap(self._h, int(cap)))
 
     def render_pass(self, seed=DEFAULT_SEED, pass_index=0, shard=(0, 1), tile_stride=1, chunk_paths=0,
                     film: np.ndarray | None = None, flags=0, ordered=False):

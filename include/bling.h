@@ -145,6 +145,25 @@ int bling_create(const int* device_ids, int n_devices, bling_ctx** out);
  * SAH BVH2 on the host, flattens triangles/shapes/materials/lights to SoA and uploads them. */
 int bling_scene_upload(bling_ctx* ctx, const bling_scene_desc* desc);
 
+/* The same upload with a choice of BVH builder.  BLING_BVH_HOST is bling_scene_upload: the binned SAH on one
+ * host thread.  BLING_BVH_DEVICE builds a linear BVH on device_ids[0] (csrc/common/lbvh.h: Morton keys, an LDS
+ * radix sort, the common-prefix hierarchy, bottom-up bounds, leaves of one or two items) in the very node and
+ * leaf format of the host tree; the BVH2 and its refs come back to the host once, and the BVH4, the threaded
+ * list, the LDS plans and the leaf records are derived from it as from the host tree.  The tree depends on the
+ * items only: the same bits on every run, equal to bling_host_lbvh (bling_host.h).  Peers of a multi-device
+ * context receive the arrays built on the first device.
+ * The device builder stands down -- the upload succeeds with the host tree, and bling_debug_bvh_build_info
+ * names the reason -- for a fractal scene, for fewer than three items, for a tree deeper than the traversal
+ * stack allows (31) and for more than 2^24 items.  flags must be 0.  A bvh_builder other than the two is
+ * BLING_EINVAL. */
+#define BLING_BVH_HOST   0u
+#define BLING_BVH_DEVICE 1u
+typedef struct bling_upload_params {
+  uint32_t bvh_builder;     /* BLING_BVH_* */
+  uint32_t flags;           /* 0 */
+} bling_upload_params;
+int bling_scene_upload_with(bling_ctx* ctx, const bling_scene_desc* desc, const bling_upload_params* params);
+
 /* The checks bling_scene_upload makes of a scene description before any device work (render
  * config, texture graphs, host-folded material spectra, lights, images), without a context or a
  * device: the parser's error path (parseJob, IO/RenderJob.hs:31-34, and the `fail` paths of
@@ -771,6 +790,30 @@ int bling_debug_compact(bling_ctx* ctx, const uint8_t* flags, const uint32_t* qu
  * NUL-terminated into buf (at most size bytes); *len (may be NULL) receives the full length.
  * Diagnostics for bench.py and the tests; no reference counterpart. */
 int bling_debug_scene_info(bling_ctx* ctx, char* buf, size_t size, size_t* len);
+
+/* Diagnostics: the uploaded scene's BVH2 as the kernels walk it, whichever builder made it, read back from
+ * device_ids[0]: 16 floats per node (two child boxes, two links, two zero words) and the leaf refs.  *n_nodes
+ * and *n_refs always receive the sizes; nodes and refs (either may be NULL) are written only when both
+ * capacities (in nodes and in refs) suffice -- BLING_EINVAL otherwise, with nothing written. */
+int bling_debug_bvh(bling_ctx* ctx, float* nodes, size_t cap_nodes, uint32_t* refs, size_t cap_refs, size_t* n_nodes,
+                    size_t* n_refs);
+
+/* Diagnostics: how the uploaded scene's BVH2 was built. */
+#define BLING_BVH_FALLBACK_NONE    0u
+#define BLING_BVH_FALLBACK_FRACTAL 1u   /* a fractal scene: its leaf order is the host tree's */
+#define BLING_BVH_FALLBACK_ITEMS   2u   /* fewer than three items */
+#define BLING_BVH_FALLBACK_DEPTH   3u   /* the linear BVH is deeper than the traversal stack allows */
+#define BLING_BVH_FALLBACK_REFS    4u   /* more items than a leaf code can address */
+typedef struct bling_bvh_build_info {
+  uint32_t requested, used;       /* BLING_BVH_* */
+  uint32_t fallback;              /* BLING_BVH_FALLBACK_*: why used differs from requested */
+  uint32_t items, nodes, depth, leaves, max_leaf;
+  double ms_build;                /* device builder: HIP events around its kernels; host builder: wall time */
+  double ms_derive;               /* host wall time of what is derived from the BVH2: BVH4, threaded list, plans, leaf records */
+} bling_bvh_build_info;
+int bling_debug_bvh_build_info(bling_ctx* ctx, bling_bvh_build_info* out);
+/* Test hook: the depth above which the device builder stands down, 1 .. 31; 0 restores 31. */
+int bling_debug_set_bvh_depth_cap(bling_ctx* ctx, int cap);
 
 /* Frees every device resource of the context. */
 void bling_destroy(bling_ctx* ctx);

@@ -154,6 +154,27 @@ int   bling_host_camera_samples(const bling_scene_desc* desc, uint32_t seed, uin
 /* rgbToSpectrumIllum (Spectrum.hs:146-159 over the illuminant bases), as the loader applies it to image maps. */
 void  bling_host_rgb_to_spectrum_illum(const float rgb[3], float out16[16]);
 
+/* ---- the host side of the device BVH builder (bling_scene_upload_with, BLING_BVH_DEVICE; bling.h) ----
+ * The linear BVH of csrc/common/lbvh.h on the CPU, with no context and no GPU: Morton keys over the boxes'
+ * centres (key = 30-bit code << 32 | item index), ascending order, the common-prefix hierarchy, leaves of one or
+ * two items, surviving nodes numbered ascending with the root as node 0.  The device builder's tree equals this
+ * one bit for bit.
+ *   boxes: n items, 6 floats each (lo.xyz, hi.xyz); refs: their n leaf reference words.  3 <= n <= 2^24.
+ *   depth_cap: the deepest tree returned, 1 .. 31; 0 = 31.
+ *   nodes_out: room for 16 (n - 1) floats; info->nodes nodes of 16 floats are written (two child boxes, two
+ *     links, two zero words: the BVH2 node the kernels walk).  refs_out: n words, the refs in sorted order.
+ *     keys_out (may be NULL): the n sorted keys.
+ * BLING_LBVH_OK; BLING_LBVH_EINVAL for a NULL argument, an n or a depth_cap out of range; BLING_LBVH_EDEPTH for
+ * a tree deeper than the cap: info->depth holds its depth, refs_out and keys_out are written, nodes_out is not. */
+#define BLING_LBVH_OK      0
+#define BLING_LBVH_EINVAL -1
+#define BLING_LBVH_EDEPTH -2
+typedef struct bling_lbvh_info {
+  uint32_t items, nodes, depth, leaves, max_leaf;
+} bling_lbvh_info;
+int   bling_host_lbvh(const float* boxes, const uint32_t* refs, size_t n, int depth_cap, float* nodes_out, uint32_t* refs_out,
+                      uint64_t* keys_out, bling_lbvh_info* info);
+
 #ifdef __cplusplus
 }
 #endif
