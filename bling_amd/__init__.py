@@ -37,3 +37,17 @@ def host_lbvh(boxes, refs, depth_cap=0, with_keys=False):
     d = {k: int(getattr(info, k)) for k, _ in info._fields_}
     out = (nodes[:d["nodes"]].copy(), refs_out, d)
     return out + (keys,) if with_keys else out
+
+
+def scene_plan(job) -> dict:
+    """bling_debug_scene_plan (include/bling.h): the acceleration / kernel plan an upload of the job would settle
+    with the host builder -- Context.scene_info()'s dict -- from the description alone, no context and no GPU.
+    render.BlingError for a description bling_scene_validate refuses."""
+    import ctypes as C
+    import json
+
+    from . import _ffi
+    from .render import _check
+    buf = C.create_string_buffer(1024)
+    _check(_ffi.hip().bling_debug_scene_plan(C.c_void_p(job.desc), buf, len(buf), None))
+    return json.loads(buf.value.decode())

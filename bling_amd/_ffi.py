@@ -283,6 +283,7 @@ HIP_SYMBOLS = ["bling_create", "bling_scene_upload", "bling_scene_validate", "bl
                "bling_surface_li_device", "bling_surface_li", "bling_debug_set_li_chunk",
                "bling_camera_samples_device", "bling_camera_samples",
                "bling_scene_upload_with", "bling_debug_bvh", "bling_debug_bvh_build_info", "bling_debug_set_bvh_depth_cap",
+               "bling_debug_scene_plan",
                "bling_destroy", "bling_last_error", "bling_version"]
 
 
@@ -431,6 +432,8 @@ def hip() -> C.CDLL:
             lib.bling_camera_samples.restype = C.c_int
         lib.bling_debug_scene_info.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
         lib.bling_debug_scene_info.restype = C.c_int
+        lib.bling_debug_scene_plan.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        lib.bling_debug_scene_plan.restype = C.c_int
         if hasattr(lib, "bling_debug_mis_culled"):    # older experiment builds lack it
             lib.bling_debug_mis_culled.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
             lib.bling_debug_mis_culled.restype = C.c_int

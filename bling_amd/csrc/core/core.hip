@@ -7,6 +7,9 @@
 //   k_film            per-tile filtered splat into LDS + merge into the film (Image.hs:108-299)
 // Path state is SoA (one 64-B record per spectrum) indexed through compacted queues.  Traversal
 // uses the LDS stack of dev_trace.h.
+// This unit holds the pass driver, the film, tile and develop calls, bling_render, the debug and trace
+// calls and the SPPM, light tracer and Metropolis entries.  What a scene becomes before a pass is planned
+// on the host in scene_plan.cpp and put on the devices by scene_upload.hip.
 #include "core_internal.h"
 #include "pass_plan.h"
 #include "pass_stats.h"
@@ -23,561 +26,6 @@ using namespace bcore;
 namespace {
 
 thread_local std::string g_err;
-
-// largest threaded BVH (child boxes) walked by the wave-coherent kernels.  A/B on MI355X
-// (DESIGN.md 3): sun-sky (8 entries) closest-hit -11 %; cornell-box (30) +28 %, so it stays per-lane
-constexpr uint32_t kPacketMaxEntries = 16;
-// primitives up to which the traversal kernels test every primitive instead of walking a tree:
-// sun-sky's 4 shapes, closest-hit 108 -> 93 ms per C4 pass; cornell's 31 primitives measured even
-// (closest 28.9 -> 28.4 ms, any-hit 8.6 -> 9.4: profiles/r05_ab_session.txt r05h-l), so they walk
-// the BVH4
-constexpr uint32_t kBruteMax = 16;
-static_assert(2 * kPacketMaxEntries <= 64, "the packet kernels hold the entry list in one VGPR float4 per lane");
-// scenes with at most this many analytic shapes keep their shape records in the BVH4 kernels' LDS
-constexpr uint32_t kLdsShapesMax = 8;
-
-// LDS plan of the traversal kernels: keep a block at <= 30 KiB so five 256-thread blocks fit a CU's
-// 160 KiB.  The stack takes depth x 1 KiB; small scenes then go to LDS whole, larger ones keep the
-// breadth-first node prefix (the top levels every ray visits).
-void plan_lds(DevScene& S, uint32_t nodes, uint32_t tris, uint32_t refs, uint32_t depth) {
-  constexpr size_t kBudget = 30 * 1024;
-  S.stack_depth = depth;
-  const size_t stack = (size_t)4 * TRACE_BLOCK * depth;
-  const size_t avail = kBudget > stack ? kBudget - stack : 0;
-  const size_t ref_b = (size_t)16 * ((refs + 3) / 4);
-  if ((size_t)64 * nodes + lds_tri_bytes(tris) + ref_b <= avail) {
-    S.lds_nodes = nodes; S.lds_tris = tris; S.lds_refs = refs;
-    return;
-  }
-  S.lds_tris = 0;
-  S.lds_refs = ref_b <= avail / 4 ? refs : 0;
-  const size_t left = avail - (S.lds_refs ? ref_b : 0);
-  S.lds_nodes = (uint32_t)std::min<size_t>(nodes, left / 64);
-}
-
-// LDS plan of the BVH4 (Traversal4): a 26-KiB block budget, so six 256-thread blocks share a CU's
-// 160 KiB -- the meshes-profile kernel's 78 VGPRs allow six waves per SIMD, and occupancy beats a
-// longer node prefix (A/B on C3, profiles/r02_ab_lds4_budget_s5.txt: 20 / 26 / 30 / 40 / 53 KiB ->
-// 5 002 / 5 046 / 4 822 / 4 518 / 3 009 Mrays/s).  When the tree,
-// triangles, refs and the whole stack bound fit, everything goes to LDS (lds_all4).  Otherwise
-// stack4_lds rows of the stack stay in LDS (12: flat from 8 to 20 rows on C3), the
-// rest spill to global rows, and the breadth-first node prefix (and the refs, if small) take what is
-// left (112 bytes a node).
-void plan_lds4(DevScene& S, uint32_t nodes, uint32_t tris, uint32_t refs, uint32_t need, uint32_t shapes) {
-  constexpr size_t kBudget = (size_t)26 * 1024;
-  const size_t ref_b = (size_t)16 * ((refs + 3) / 4);
-  S.stack4_need = need;
-  // shape records (176 B each) go to LDS whole when the scene has a few: cornell's light quad
-  const uint32_t sh = shapes <= kLdsShapesMax ? shapes : 0u;
-  S.lds4_shapes = sh;
-  // all in LDS: decided with the size the all-LDS kernels launch with (their leaf-order layout and
-  // its two spare stack rows), so an lds_all4 block never exceeds the budget
-  if (lds_bytes4_leaf(nodes, refs, need, sh) <= kBudget) {
-    S.lds4_nodes = nodes; S.lds4_tris = tris; S.lds4_refs = refs; S.stack4_lds = need;
-    return;
-  }
-  const uint32_t rows = std::max(1u, std::min(12u, need));
-  S.stack4_lds = rows;
-  const size_t stack = (size_t)4 * TRACE_BLOCK * rows + sizeof(DevShape) * sh;
-  const size_t avail = kBudget > stack ? kBudget - stack : 0;
-  S.lds4_tris = 0;
-  S.lds4_refs = ref_b <= avail / 4 ? refs : 0;
-  const size_t left = avail - (S.lds4_refs ? ref_b : 0);
-  S.lds4_nodes = (uint32_t)std::min<size_t>(nodes, left / 112);
-}
-
-// Everything upload_scene and the kernels assume of a scene description, checked on the host before
-// any device work (bling_scene_validate runs it without a device): render config, texture graphs
-// (computed textures at the top, their children stored), host-folded material spectra, light
-// count, images and the textures and environment maps that index them.
-void validate_scene(const bling_scene_desc* d) {
-  if (!d) throw std::invalid_argument("null argument");
-  if (d->config.width <= 0 || d->config.height <= 0) throw std::invalid_argument("bad render config");
-  if (d->config.renderer == BLING_RENDERER_SPPM) {
-    // eye trees are walked depth-first with one parked sibling per level (k_sppm_eye)
-    if (d->config.max_depth < 1 || d->config.max_depth > SPPM_MAX_DEPTH)
-      throw std::invalid_argument("sppm maxDepth outside [1, " + std::to_string(SPPM_MAX_DEPTH) + "]");
-    if (d->config.sppm_photons < 1 || d->config.sppm_threads < 1) throw std::invalid_argument("bad sppm photon count");
-  } else if (d->config.renderer == BLING_RENDERER_LIGHT) {
-    if (d->light.pass_photons < 1) throw std::invalid_argument("light tracer passPhotons < 1");
-  } else if (d->config.renderer == BLING_RENDERER_METROPOLIS) {
-    const bling_metropolis& m = d->metropolis;
-    // the chain's integrator is the bidirectional one with maxDepth = sampleDepth (Metropolis.hs:46-49)
-    if (m.max_depth < 1 || m.max_depth > BD_MAX_DEPTH)
-      throw std::invalid_argument("metropolis maxDepth outside [1, " + std::to_string(BD_MAX_DEPTH) + "]");
-    if (m.bootstrap < 1) throw std::invalid_argument("metropolis bootstrap < 1");
-    const float mut = mlt_mutations(m, d->config.width, d->config.height);
-    if (!(mut >= 1.f)) throw std::invalid_argument("metropolis mpp gives no mutation (floor (mpp * nPixels) < 1)");
-    if (!(mut < 2147483648.f)) throw std::invalid_argument("metropolis mpp gives 2^31 mutations or more");
-    if (m.chains < 1) throw std::invalid_argument("metropolis chains < 1");
-    if ((uint32_t)m.chains > MLT_MAX_CHAINS) throw std::invalid_argument("metropolis chains > 2^20");
-  } else if (d->config.spp <= 0) {
-    throw std::invalid_argument("bad render config");
-  } else if (d->config.integrator == BLING_INTEGRATOR_DIRECT) {
-    // the tree is walked depth-first with one parked sibling per level (k_shade_dl): bound it
-    if (d->config.max_depth < 1 || d->config.max_depth > kMaxDlDepth)
-      throw std::invalid_argument("directLighting maxDepth outside [1, " + std::to_string(kMaxDlDepth) + "]");
-  } else if (d->config.integrator == BLING_INTEGRATOR_BIDIR) {
-    // both subpaths' specular masks are 16-bit words, the vertex buffers 2 maxDepth records (bidir.h)
-    if (d->config.max_depth < 1 || d->config.max_depth > BD_MAX_DEPTH)
-      throw std::invalid_argument("bidir maxDepth outside [1, " + std::to_string(BD_MAX_DEPTH) + "]");
-    if (d->config.sample_depth < 0) throw std::invalid_argument("bidir sampleDepth < 0");
-  } else if (d->config.integrator != BLING_INTEGRATOR_PATH && d->config.integrator != BLING_INTEGRATOR_NORMALS) {
-    throw std::invalid_argument("unknown surface integrator");
-  }
-  for (uint32_t k = 0; k < d->num_textures; ++k) {     // computed textures: children the device resolves
-    const bling_texture& t = d->textures[k];
-    auto simple = [&](int32_t ti) {
-      return ti >= 0 && (uint32_t)ti < d->num_textures && d->textures[ti].kind <= BLING_TEX_GRAPHPAPER;
-    };
-    auto stex_ok = [&](int32_t si) { return si >= 0 && (uint32_t)si < d->num_scalar_textures; };
-    bool ok = true;
-    if (t.kind == BLING_TEX_BLEND) ok = simple(t.tex1) && simple(t.tex2) && stex_ok(t.stex);
-    else if (t.kind == BLING_TEX_CHECKER) ok = simple(t.tex1) && simple(t.tex2);
-    else if (t.kind == BLING_TEX_GRADIENT) {
-      ok = t.tex2 >= 1 && t.tex1 >= 0 && (uint64_t)t.tex1 + (uint64_t)t.tex2 <= d->num_textures && stex_ok(t.stex);
-      for (int32_t s = 0; ok && s < t.tex2; ++s) ok = d->textures[t.tex1 + s].kind == BLING_TEX_CONST;
-    } else if (t.kind == BLING_TEX_GRAPHPAPER) ok = simple(t.tex1) && simple(t.tex2);
-    else ok = t.kind == BLING_TEX_CONST || t.kind == BLING_TEX_IMAGE;   // the image index is checked below
-    if (!ok) throw std::invalid_argument("texture " + std::to_string(k) + ": malformed or nested computed texture");
-  }
-  for (uint32_t k = 0; k < d->num_scalar_textures; ++k) {
-    const bling_scalar_texture& t = d->scalar_textures[k];
-    bool ok = t.kind >= BLING_STEX_CONST && t.kind <= BLING_STEX_IMAGE;
-    if (t.kind == BLING_STEX_SCALE) ok = t.child >= 0 && (uint32_t)t.child < d->num_scalar_textures;
-    if (t.kind == BLING_STEX_CRYSTAL)
-      ok = t.octaves >= 1 && t.child >= 0 && (uint64_t)t.child + (uint64_t)t.octaves <= d->num_scalar_textures;
-    if (!ok) throw std::invalid_argument("scalar texture " + std::to_string(k) + ": malformed");
-  }
-  for (uint32_t k = 0; k < d->num_materials; ++k) {
-    // the encoding of bling_scene.h ("materials"): every texture a kind reads is in range; a scalar
-    // slot's stex is a scalar texture or -1; a transformed spectrum slot is either folded (a constant
-    // record make_bsdf reads directly) or raw (any texture eval_spectrum serves at the top of a slot,
-    // which the texture loop above established for every record)
-    const bling_material& m = d->materials[k];
-    const std::string who = "material " + std::to_string(k);
-    int nt = 0, ns = 1;                                   // textures read, scalar slots with an stex
-    bool raw[4] = {true, true, true, true};               // untransformed slots take any texture
-    auto flag = [&](int j) {
-      if (m.stex[j] != -1 && m.stex[j] != BLING_SLOT_RAW) throw std::invalid_argument(who + ": bad raw-slot flag in stex[" + std::to_string(j) + "]");
-      return m.stex[j] == BLING_SLOT_RAW;
-    };
-    switch (m.kind) {
-      case BLING_MAT_BLACKBODY: ns = 0; break;
-      case BLING_MAT_MATTE: nt = 1; break;
-      case BLING_MAT_PLASTIC: case BLING_MAT_GLASS: case BLING_MAT_METAL: nt = 2; break;
-      case BLING_MAT_MIRROR: nt = 1; ns = 0; break;
-      case BLING_MAT_TRANSMATTE: nt = 2; raw[0] = raw[1] = flag(1); break;
-      case BLING_MAT_SHINYMETAL:
-        nt = 4; raw[0] = raw[1] = flag(1); raw[2] = raw[3] = flag(2);
-        if ((raw[0] && m.tex[0] != m.tex[1]) || (raw[2] && m.tex[2] != m.tex[3]))
-          throw std::invalid_argument(who + ": a raw shinyMetal spectrum must sit in both of its slots");
-        break;
-      case BLING_MAT_SUBSTRATE: nt = 3; ns = 3; break;    // raw or folded by the texture's kind
-      default: throw std::invalid_argument(who + ": unknown kind");
-    }
-    for (int j = 0; j < nt; ++j) {
-      const int32_t ti = m.tex[j];
-      if (ti < 0 || (uint32_t)ti >= d->num_textures)
-        throw std::invalid_argument(who + ": texture " + std::to_string(j) + " out of range");
-      if (!raw[j] && d->textures[ti].kind != BLING_TEX_CONST)
-        throw std::invalid_argument(who + ": texture " + std::to_string(j) + " is marked folded but is no constant spectrum");
-    }
-    for (int j = 0; j < 4; ++j) {
-      if (!(j < ns || j == 3)) continue;                  // stex[3]: bump
-      if (m.stex[j] < -1 || (m.stex[j] >= 0 && (uint32_t)m.stex[j] >= d->num_scalar_textures))
-        throw std::invalid_argument(who + ": scalar texture " + std::to_string(j) + " out of range");
-    }
-  }
-  // the path state packs a light index (and a hit light + 1) into 8 bits each (wavefront.h vf_*)
-  if (d->num_lights > 254) throw std::invalid_argument("more than 254 lights");
-  for (uint32_t k = 0; k < d->num_lights; ++k) {
-    const bling_light& l = d->lights[k];
-    if (l.kind == BLING_LIGHT_INFINITE && l.env_kind == BLING_ENV_IMAGE && (l.env_w <= 0 || l.env_h <= 0 || !l.env_texels))
-      throw std::invalid_argument("infinite light: empty image map");
-  }
-  for (uint32_t k = 0; k < d->num_images; ++k) {
-    const bling_image& im = d->images[k];
-    if (im.width <= 0 || im.height <= 0 || !im.texels || (im.channels != 1 && im.channels != 16))
-      throw std::invalid_argument("texture image: bad size, channels or texels");
-  }
-  for (uint32_t k = 0; k < d->num_textures; ++k) {
-    const bling_texture& t = d->textures[k];
-    if (t.kind == BLING_TEX_IMAGE && (t.tex1 < 0 || (uint32_t)t.tex1 >= d->num_images || d->images[t.tex1].channels != 16))
-      throw std::invalid_argument("image texture " + std::to_string(k) + ": no spectral image");
-  }
-  for (uint32_t k = 0; k < d->num_scalar_textures; ++k) {
-    const bling_scalar_texture& t = d->scalar_textures[k];
-    if (t.kind == BLING_STEX_IMAGE && (t.child < 0 || (uint32_t)t.child >= d->num_images || d->images[t.child].channels != 1))
-      throw std::invalid_argument("scalar image texture " + std::to_string(k) + ": no greyscale image");
-  }
-}
-
-// one thread per triangle: its shading frame (dev_shade.h tri_frame_build)
-__global__ void k_tri_frames(const float* __restrict__ pts, const float* __restrict__ uvs, float4* __restrict__ out,
-                             uint32_t n) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < n) tri_frame_build(pts + (size_t)9 * t, uvs + (size_t)6 * t, out + (size_t)4 * t);
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-// The BVH2 of the items by the builder asked for (BLING_BVH_*), and how it came about.  The device builder
-// (bvh_device.hip) stands down for what bling.h lists; the host's binned SAH then builds as it always did.
-bvh::Result build_bvh2(bling_ctx* c, const std::vector<bvh::Box>& boxes, const std::vector<uint32_t>& refs, bool fractal,
-                       uint32_t builder, bling_bvh_build_info* info) {
-  *info = bling_bvh_build_info{};
-  info->requested = info->used = builder;
-  info->items = (uint32_t)boxes.size();
-  bvh::Result R;
-  if (builder == BLING_BVH_DEVICE) {
-    const int cap = c->bvh_depth_cap ? c->bvh_depth_cap : STACK_DEPTH - 1;
-    if (fractal) info->fallback = BLING_BVH_FALLBACK_FRACTAL;
-    else if (boxes.size() < 3) info->fallback = BLING_BVH_FALLBACK_ITEMS;
-    else if (boxes.size() > ((size_t)1 << 24)) info->fallback = BLING_BVH_FALLBACK_REFS;
-    else {
-      float ms = 0.f;
-      int depth = 0;
-      if (lbvh_build_device(c, boxes, refs, cap, R, &ms, &depth)) { info->ms_build = ms; return R; }
-      info->fallback = BLING_BVH_FALLBACK_DEPTH;
-    }
-    info->used = BLING_BVH_HOST;
-  }
-  // Leaves of at most two primitives: the all-LDS BVH4 kernel tests two primitives per step, so a
-  // leaf costs one step (A/B, profiles/r02_ab_bvh_leaf_s5.txt: C2 closest-hit 37.4 -> 31.5 ms per
-  // pass against leaves of up to 4; C3, C4 and C5 within noise).
-  const auto t0 = std::chrono::steady_clock::now();
-  R = bvh::build(boxes, refs, 2);
-  info->ms_build = ms_since(t0);
-  return R;
-}
-
-// given: the BVH2 another context of the fan-out built for this scene (peers), or nullptr to build it here
-// with `builder`; keep (may be nullptr) receives a copy of the tree built here.
-void upload_scene(bling_ctx* c, const bling_scene_desc* d, uint32_t builder, const bvh::Result* given, bvh::Result* keep) {
-  HIPCHK(hipSetDevice(c->device));
-  DevScene& S = c->S;
-  S = DevScene{};
-  const uint32_t nt = d->num_triangles, ns = d->num_shapes;
-  // --- triangles: MT record (v0, e1 = p2 - p1, e2 = p3 - p1) and shading data
-  std::vector<float4> geo((size_t)3 * nt);
-  std::vector<float> pts((size_t)9 * nt);
-  for (uint32_t t = 0; t < nt; ++t) {
-    const uint32_t* ix = d->tri_indices + 3 * t;
-    float p[3][3];
-    for (int k = 0; k < 3; ++k)
-      for (int a = 0; a < 3; ++a) { p[k][a] = d->vertices[3 * ix[k] + a]; pts[9 * t + 3 * k + a] = p[k][a]; }
-    float e1[3], e2[3];
-    for (int a = 0; a < 3; ++a) { e1[a] = p[1][a] - p[0][a]; e2[a] = p[2][a] - p[0][a]; }
-    geo[3 * t + 0] = make_float4(p[0][0], p[0][1], p[0][2], e1[0]);
-    geo[3 * t + 1] = make_float4(e1[1], e1[2], e2[0], e2[1]);
-    geo[3 * t + 2] = make_float4(e2[2], 0.f, 0.f, 0.f);
-  }
-  c->tri_geo.upload(geo.data(), geo.size());
-  {                                   // per-triangle shading frames (dev_shade.h tri_frame_build)
-    DBuf<float> dpts, duvs;
-    dpts.upload(pts.data(), pts.size());
-    duvs.upload(d->tri_uvs, (size_t)6 * nt);
-    c->tri_frame.alloc((size_t)4 * nt);
-    if (nt) {
-      k_tri_frames<<<(nt + 255) / 256, 256, 0, c->stream>>>(dpts.p, duvs.p, c->tri_frame.p, nt);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipStreamSynchronize(c->stream));
-    }
-  }
-  c->tri_material.upload(d->tri_material, nt);
-  if (d->tri_normals && d->tri_has_normals) {
-    c->tri_normals.upload(d->tri_normals, (size_t)9 * nt);
-    c->tri_has_n.upload(d->tri_has_normals, nt);
-  } else { c->tri_normals.free(); c->tri_has_n.free(); }
-  // --- primitive list (reference order) -> BVH items
-  std::vector<int32_t> tri_prim(nt, -1), shape_prim(ns, -1);
-  int32_t fractal_prim = -1;
-  std::vector<bvh::Box> boxes;
-  std::vector<uint32_t> refs;
-  for (uint32_t i = 0; i < d->num_prims; ++i) {
-    int kind = d->prim_kind[i], idx = d->prim_index[i];
-    bvh::Box b;
-    for (int a = 0; a < 3; ++a) { b.lo[a] = INFINITY; b.hi[a] = -INFINITY; }
-    if (kind == 0) {
-      tri_prim[idx] = (int32_t)i;
-      for (int k = 0; k < 3; ++k)
-        for (int a = 0; a < 3; ++a) { float v = pts[9 * idx + 3 * k + a]; b.lo[a] = std::min(b.lo[a], v); b.hi[a] = std::max(b.hi[a], v); }
-      refs.push_back((REF_TRI << 30) | (uint32_t)idx);
-    } else if (kind == 1) {
-      shape_prim[idx] = (int32_t)i;
-      const bling_shape& s = d->shapes[idx];
-      float mn[3], mx[3];
-      const float* P = s.params;                                   // objectBounds (Shape.hs:299-311)
-      if (s.kind == BLING_SHAPE_QUAD) { mn[0] = -P[0]; mn[1] = -P[1]; mn[2] = 0.f; mx[0] = P[0]; mx[1] = P[1]; mx[2] = 0.f; }
-      else if (s.kind == BLING_SHAPE_DISK) { mn[0] = -P[1]; mn[1] = -P[1]; mn[2] = P[0]; mx[0] = P[1]; mx[1] = P[1]; mx[2] = P[0]; }
-      else if (s.kind == BLING_SHAPE_CYLINDER) { mn[0] = -P[0]; mn[1] = -P[0]; mn[2] = P[1]; mx[0] = P[0]; mx[1] = P[0]; mx[2] = P[2]; }
-      else if (s.kind == BLING_SHAPE_BOX) { for (int a = 0; a < 3; ++a) { mn[a] = P[a]; mx[a] = P[3 + a]; } }
-      else { for (int a = 0; a < 3; ++a) { mn[a] = -P[0]; mx[a] = P[0]; } }
-      for (int cidx = 0; cidx < 8; ++cidx) {
-        float q[3] = {(cidx & 4) ? mx[0] : mn[0], (cidx & 2) ? mx[1] : mn[1], (cidx & 1) ? mx[2] : mn[2]};
-        const float* m = s.o2w;
-        float w = m[12] * q[0] + m[13] * q[1] + m[14] * q[2] + m[15];
-        for (int a = 0; a < 3; ++a) {
-          float v = m[4 * a] * q[0] + m[4 * a + 1] * q[1] + m[4 * a + 2] * q[2] + m[4 * a + 3];
-          if (w != 1.f) v /= w;
-          b.lo[a] = std::min(b.lo[a], v); b.hi[a] = std::max(b.hi[a], v);
-        }
-      }
-      refs.push_back((REF_SHAPE << 30) | (uint32_t)idx);
-    } else {
-      fractal_prim = (int32_t)i;
-      const float fr = d->fractal.kind == BLING_FRACTAL_JULIA ? 1.7321f : 1.4143f;   // entry spheres r^2 = 3 / 2
-      for (int a = 0; a < 3; ++a) { b.lo[a] = -fr; b.hi[a] = fr; }
-      refs.push_back((REF_FRACTAL << 30));
-    }
-    boxes.push_back(b);
-  }
-  {
-    // worldBounds of the reference's kd-tree (union of the primitive bounds; the fractals' are
-    // mkMandelBulb's +-2.5 and the Julia radius sqrt 3, not the tighter BVH entry spheres)
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (uint32_t i = 0; i < d->num_prims; ++i) {
-      bvh::Box b = boxes[i];
-      if (d->prim_kind[i] == 2) {
-        const float fr = d->fractal.kind == BLING_FRACTAL_JULIA ? sqrtf(3.f) : 2.5f;
-        for (int a = 0; a < 3; ++a) { b.lo[a] = -fr; b.hi[a] = fr; }
-      }
-      for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], b.lo[a]); hi[a] = std::max(hi[a], b.hi[a]); }
-    }
-    float dd[3];
-    for (int a = 0; a < 3; ++a) { S.world_c[a] = lo[a] + (hi[a] - lo[a]) * 0.5f; dd[a] = hi[a] - S.world_c[a]; }
-    S.world_r = sqrtf(dd[0] * dd[0] + dd[1] * dd[1] + dd[2] * dd[2]);
-    for (int a = 0; a < 3; ++a) { S.kd_lo[a] = lo[a]; S.kd_hi[a] = hi[a]; }
-  }
-  bling_bvh_build_info info{};
-  const bvh::Result R = given ? *given : build_bvh2(c, boxes, refs, fractal_prim >= 0, builder, &info);
-  if (keep) *keep = R;
-  const auto t_derive = std::chrono::steady_clock::now();
-  c->nodes.upload(reinterpret_cast<const float4*>(R.nodes.data()), R.nodes.size() / 4);
-  c->refs.upload(R.refs.data(), R.refs.size());
-  {
-    // the primitives' records in leaf order, the ref in each, one zero record behind them (the layout:
-    // dev_trace.h LeafRec).  The BVH4 kernels with a global fallback test a leaf primitive with one
-    // dependent load instead of two; the all-LDS kernels copy the records into LDS as they are.
-    std::vector<float4> lg(leaf_geo_quads((uint32_t)R.refs.size()), make_float4(0.f, 0.f, 0.f, 0.f));
-    for (size_t j = 0; j < R.refs.size(); ++j) {
-      const uint32_t ref = R.refs[j], idx = ref & 0x3FFFFFFFu;
-      if ((ref >> 30) == REF_TRI) { lg[3 * j] = geo[3 * idx]; lg[3 * j + 1] = geo[3 * idx + 1]; }
-      float rf;
-      std::memcpy(&rf, &ref, sizeof rf);
-      lg[3 * j + 2] = make_float4((ref >> 30) == REF_TRI ? geo[3 * idx + 2].x : 0.f, rf, 0.f, 0.f);
-    }
-    c->leaf_geo.upload(lg.data(), lg.size());
-    if (c->leaf_geo.n != (size_t)3 * (R.refs.size() + 1)) throw std::runtime_error("leaf_geo: not 3 x (refs + 1) records");
-  }
-  c->bvh_depth = R.depth; c->bvh_leaves = R.leaves; c->bvh_max_leaf = R.max_leaf;
-  if (R.depth > STACK_DEPTH - 1) throw std::runtime_error("BVH deeper than the traversal stack");
-  c->features = bfeat::scene_features(d);
-  static_assert(FT_PROCTEX == bfeat::PROCTEX && FT_BUMP == bfeat::BUMP && FT_MATTE == bfeat::MATTE &&
-                FT_MULTI_LIGHT == bfeat::MULTI_LIGHT, "feature bits");
-  plan_lds(S, (uint32_t)(R.nodes.size() / 16), nt, (uint32_t)R.refs.size(), (uint32_t)R.depth + 1);
-  c->lds_trace = lds_bytes(S.lds_nodes, S.lds_tris, S.lds_refs, S.stack_depth);
-  c->lds_all = S.lds_nodes == (uint32_t)(R.nodes.size() / 16) && S.lds_tris == nt && S.lds_refs == (uint32_t)R.refs.size();
-  {
-    // the 4-wide tree for the queue traversal kernels of non-fractal profiles (Traversal4)
-    const bvh::Result4 Q = bvh::collapse4(R);
-    const uint32_t n4 = (uint32_t)(Q.nodes.size() / 28);
-    plan_lds4(S, n4, nt, (uint32_t)R.refs.size(), (uint32_t)std::max(1, Q.stack_need), ns);
-    c->lds_all4 = S.lds4_nodes == n4 && S.lds4_tris == nt && S.lds4_refs == (uint32_t)R.refs.size() &&
-                  S.stack4_lds == S.stack4_need && S.lds4_shapes == ns;
-    // the all-LDS kernels lay the primitives out in leaf order (dev_trace.h lds_setup<..., LEAF>)
-    c->lds_trace4 = c->lds_all4 ? lds_bytes4_leaf(S.lds4_nodes, S.lds4_refs, S.stack4_lds, S.lds4_shapes)
-                                : lds_bytes4(S.lds4_nodes, S.lds4_tris, S.lds4_refs, S.stack4_lds, S.lds4_shapes);
-    c->nodes4.upload(reinterpret_cast<const float4*>(Q.nodes.data()), Q.nodes.size() / 4);
-    c->bvh4_depth = Q.depth;
-    S.num_nodes4 = n4;
-    S.stack4_lanes = 0;
-    if (S.stack4_need > S.stack4_lds) {
-      int cus = 256;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) cus = 256;
-      S.stack4_lanes = (uint32_t)cus * 2048u;           // every resident lane of a persistent grid
-      c->stack4_ovf.alloc((size_t)(S.stack4_need - S.stack4_lds) * S.stack4_lanes);
-    } else {
-      c->stack4_ovf.free();
-    }
-  }
-  {
-    // small scenes walk the threaded BVH wave-coherently (packet_walk, dev_trace.h): at most
-    // kPacketMaxEntries child boxes, no fractal
-    const std::vector<float> th = bvh::threaded(R);
-    const uint32_t ne = (uint32_t)(th.size() / 8);
-    const bool on = fractal_prim < 0 && ne > 0 && ne <= kPacketMaxEntries;
-    c->pkt.upload(reinterpret_cast<const float4*>(th.data()), th.size() / 4);
-    S.pkt = as_global(c->pkt.p);
-    S.pkt_n = on ? ne : 0u;
-    S.pkt_refs = (uint32_t)R.refs.size();
-    S.sample_major = on ? 1u : 0u;       // k_raygen's slot order: see there
-  }
-  {
-    // scenes of at most kBruteMax primitives test all of them per ray (brute_walk, dev_trace.h) instead
-    // of walking a tree; BLING_BRUTE=<n> sets the limit (0: never), for A/B measurements
-    const char* env = std::getenv("BLING_BRUTE");
-    const uint32_t lim = env ? (uint32_t)std::strtoul(env, nullptr, 10) : kBruteMax;
-    const bool on = fractal_prim < 0 && nt + ns > 0 && nt + ns <= lim && R.refs.size() == (size_t)nt + ns;
-    S.bf_tris = on ? nt : 0u;
-    S.bf_shapes = on ? ns : 0u;
-  }
-  if (!given) {
-    info.nodes = (uint32_t)(R.nodes.size() / 16);
-    info.depth = (uint32_t)R.depth; info.leaves = (uint32_t)R.leaves; info.max_leaf = (uint32_t)R.max_leaf;
-    info.ms_derive = ms_since(t_derive);
-    c->bvh_info = info;
-  }
-  c->tri_prim.upload(tri_prim.data(), nt);
-  c->shape_prim.upload(shape_prim.data(), ns);
-  // --- shapes
-  std::vector<DevShape> sh(ns);
-  for (uint32_t k = 0; k < ns; ++k) {
-    const bling_shape& s = d->shapes[k];
-    sh[k].kind = s.kind; sh[k].material = s.material; sh[k].light = s.light; sh[k].prim = shape_prim[k];
-    std::memcpy(sh[k].params, s.params, sizeof sh[k].params);
-    std::memcpy(sh[k].w2o, s.w2o, 64);
-    std::memcpy(sh[k].o2w, s.o2w, 64);
-  }
-  c->shapes.upload(sh.data(), ns);
-  // The MIS cull (wavefront.h mis_cull_test) tests the sampled area light's own shape only: it holds
-  // when no other shape carries that light.  The loader pairs them one to one; a hand-made
-  // description that does not renders without the cull.
-  c->mis_cull_ok = true;
-  for (uint32_t k = 0; k < ns; ++k) {
-    const int l = d->shapes[k].light;
-    if (l >= 0 && !((uint32_t)l < d->num_lights && d->lights[l].kind == BLING_LIGHT_AREA && d->lights[l].shape == (int)k))
-      c->mis_cull_ok = false;
-  }
-  c->materials.upload(d->materials, d->num_materials);
-  c->textures.upload(d->textures, d->num_textures);
-  c->stex.upload(d->scalar_textures, d->num_scalar_textures);
-  // --- lights: rewrite the Dist2D pointers to device copies
-  // the path state packs a light index (and a hit light + 1) into 8 bits each (wavefront.h vf_*)
-  std::vector<bling_light> lights(d->lights, d->lights + d->num_lights);
-  c->light_arrays.clear();
-  auto up = [&](const float* h, size_t n) -> const float* {
-    if (!h || !n) return nullptr;
-    c->light_arrays.emplace_back(new DBuf<float>());
-    c->light_arrays.back()->upload(h, n);
-    return c->light_arrays.back()->p;
-  };
-  // Each CDF travels with a guide table behind it (the device layout of dev_shade.h
-  // sample_c1d): g[k] = the first index whose CDF value is >= k / kCdfGuide (k = 0 .. kCdfGuide),
-  // so a search for u starts in [g[floor(u kCdfGuide)], g[floor(u kCdfGuide) + 1]] instead of the
-  // whole row (the sun-sky map's 641-entry rows: 10 dependent loads -> 1 to 3).  The marginal
-  // buffer also carries the sky's Perez denominators (host libm, as the oracle evaluates them).
-  auto with_guide = [&](const float* cdf, size_t n, size_t rows, std::vector<float>& out) {
-    out.assign(cdf, cdf + n * rows);
-    for (size_t r = 0; r < rows; ++r) {
-      const float* row = cdf + r * n;
-      size_t i = 0;
-      for (int k = 0; k <= kCdfGuide; ++k) {
-        const float t = (float)k / (float)kCdfGuide;
-        while (i < n && !(row[i] >= t)) ++i;
-        uint32_t gi = (uint32_t)i;
-        float f;
-        std::memcpy(&f, &gi, 4);
-        out.push_back(f);
-      }
-    }
-  };
-  for (auto& l : lights) {
-    if (l.kind != BLING_LIGHT_INFINITE) continue;
-    size_t nu = l.dist_nu, nv = l.dist_nv;
-    std::vector<float> rows, marg;
-    with_guide(l.dist_cdf, nu + 1, nv, rows);
-    with_guide(l.marg_cdf, nv + 1, 1, marg);
-    float den[3] = {0.f, 0.f, 0.f};
-    if (l.env_kind == BLING_ENV_SUNSKY) {
-      const float* ps[3] = {l.perez_x, l.perez_y, l.perez_Y};
-      const float st = l.sun_theta, cst = bcr::cosf(st);
-      for (int k = 0; k < 3; ++k) {                  // perez's denominator (SunSky.hs:81-86)
-        const float* q = ps[k];
-        den[k] = (1.f + q[0] * bcr::expf(q[1])) * (1.f + q[2] * bcr::expf(q[3] * st)) + q[4] * cst * cst;
-      }
-    }
-    marg.insert(marg.end(), den, den + 3);
-    if (l.env_kind == BLING_ENV_IMAGE) {
-      l.env_texels = up(l.env_texels, (size_t)l.env_w * l.env_h * 16);
-    }
-    l.dist_func = up(l.dist_func, nu * nv);
-    l.dist_cdf = up(rows.data(), rows.size());
-    l.dist_func_int = up(l.dist_func_int, nv);
-    l.marg_func = up(l.marg_func, nv);
-    l.marg_cdf = up(marg.data(), marg.size());
-  }
-  c->lights.upload(lights.data(), lights.size());
-  // --- texture images: texel tables in device memory
-  std::vector<bling_image> images(d->images, d->images + d->num_images);
-  for (auto& im : images) im.texels = up(im.texels, (size_t)im.width * im.height * im.channels);
-  c->images.upload(images.data(), images.size());
-  // --- DevScene
-  S.nodes = as_global(c->nodes.p); S.leaf_refs = as_global(c->refs.p); S.leaf_geo = as_global(c->leaf_geo.p); S.num_nodes = (uint32_t)c->nodes.n / 4;
-  S.nodes4 = as_global(c->nodes4.p); S.stack4_ovf = c->stack4_ovf.p;
-  S.tri_geo = as_global(c->tri_geo.p); S.tri_frame = as_global(c->tri_frame.p);
-  S.tri_normals = as_global(c->tri_normals.p); S.tri_has_n = as_global(c->tri_has_n.p);
-  S.tri_material = as_global(c->tri_material.p); S.tri_prim = as_global(c->tri_prim.p);
-  S.shapes = as_global(c->shapes.p);
-  S.fractal = d->fractal; S.fractal_prim = fractal_prim;
-  {
-    long long pw = 1;                     // order ^ k is a Haskell Int: 8^14 needs 64 bits
-    for (int k = 0; k < 32; ++k) { S.fractal_pw[k] = (float)pw; pw *= (long long)d->fractal.order; }
-    if (d->fractal.present && (d->fractal.iterations < 0 || d->fractal.iterations > 32))
-      throw std::runtime_error("fractal iterations outside [0, 32]");
-  }
-  S.materials = as_global(c->materials.p); S.textures = as_global(c->textures.p); S.stex = as_global(c->stex.p); S.lights = as_global(c->lights.p);
-  S.images = as_global(c->images.p);
-  S.num_lights = (int32_t)d->num_lights;
-  S.camera = d->camera;
-  std::memcpy(S.lt_w2r, d->light.w2r, sizeof S.lt_w2r);
-  S.lt_pixel_area = d->light.pixel_area;
-  std::memcpy(S.filter_table, d->filter.table, sizeof S.filter_table);
-  S.filter_w = d->filter.width; S.filter_h = d->filter.height;
-  const bling_render_config& cfg = d->config;
-  S.sampler = cfg.sampler; S.nu = cfg.nu; S.nv = cfg.nv; S.spp = cfg.spp;
-  S.max_depth = cfg.max_depth; S.sample_depth = cfg.sample_depth;
-  S.integrator = cfg.integrator;
-  if (cfg.renderer == BLING_RENDERER_METROPOLIS) {                   // mkBidirPathIntegrator md md (Metropolis.hs:46-49)
-    S.integrator = BLING_INTEGRATOR_BIDIR;
-    S.max_depth = S.sample_depth = d->metropolis.max_depth;
-  }
-  if (S.integrator == BLING_INTEGRATOR_DIRECT) S.n1d = S.n2d = 2 * cfg.max_depth;   // DirectLighting.hs:17-18
-  else if (S.integrator == BLING_INTEGRATOR_BIDIR) { S.n1d = 12 * S.sample_depth + 1; S.n2d = 9 * S.sample_depth + 2; }   // BidirPath.hs:44-48
-  else if (S.integrator == BLING_INTEGRATOR_NORMALS) { S.n1d = S.n2d = 0; S.max_depth = S.sample_depth = 0; }   // SurfaceIntegrator li 0 0 (Debug.hs:26)
-  else { S.n1d = 4 * cfg.sample_depth; S.n2d = 3 * cfg.sample_depth; }              // Path.hs:26-28
-  if (cfg.spp > (1 << 24)) throw std::runtime_error("more than 2^24 samples per pixel (the sampler's permutation, counter_rng.h)");
-  S.fd_spp = FastDiv::make((uint32_t)std::max(1, cfg.spp));
-  S.fd_nu = FastDiv::make((uint32_t)std::max(1, cfg.nu));
-  {
-    uint32_t w = (uint32_t)std::max(1, cfg.spp) - 1u;                 // brng::permute's mask
-    w |= w >> 1; w |= w >> 2; w |= w >> 4; w |= w >> 8; w |= w >> 16;
-    S.perm_mask_spp = w;
-  }
-  S.inv_spp = 1.f / (float)cfg.spp; S.inv_nu = 1.f / (float)cfg.nu; S.inv_nv = 1.f / (float)cfg.nv;
-  S.width = cfg.width; S.height = cfg.height;
-  float fw = d->filter.width, fh = d->filter.height;
-  S.ex0 = (int)floorf(0.5f - fw); S.ex1 = (int)floorf(0.5f + (float)cfg.width + fw);      // Image.hs:162-168
-  S.ey0 = (int)floorf(0.5f - fh); S.ey1 = (int)floorf(0.5f + (float)cfg.height + fh);
-  S.ext_w = S.ex1 - S.ex0 + 1;
-  c->num_prims = d->num_prims;
-  if ((int)std::ceil(fw) + 17 > FILM_TILE_MAX || (int)std::ceil(fh) + 17 > FILM_TILE_MAX)
-    throw std::runtime_error("filter wider than the LDS film tile supports");
-  c->counters.alloc(1);
-  c->dscene.upload(&S, 1);
-  c->film_dev.free();
-  c->cfg = cfg;
-  c->lt = d->light;
-  c->mp = d->metropolis;
-  c->sppm.free_all();
-  c->light.free_all();
-  c->mlt.free_all();
-  c->merge.free_all();                   // the record budget stays: it belongs to the context
-  c->mlt_boot_override.clear();
-}
 
 // A pass whose paths fit one wave runs as two half-waves on two streams (core_wave.h run_wave_pair_t)
 // where that measured faster: the cornell profile; BLING_PASS_NO_PIPELINE and
@@ -1035,70 +483,6 @@ int bling_create(const int* device_ids, int n_devices, bling_ctx** out) {
   });
 }
 
-int bling_scene_upload_with(bling_ctx* c, const bling_scene_desc* d, const bling_upload_params* up) {
-  return guarded([&] {
-    if (!c || !d || !up) throw std::invalid_argument("null argument");
-    if (up->bvh_builder != BLING_BVH_HOST && up->bvh_builder != BLING_BVH_DEVICE) throw std::invalid_argument("unknown BVH builder");
-    if (up->flags != 0u) throw std::invalid_argument("unknown upload flags");
-    validate_scene(d);
-    // no pass may mix a new scene on one device with an old or half-uploaded one on another: the
-    // context and every peer lose their scene first and get it back only once all uploads succeeded
-    c->has_scene = false;
-    for (auto& q : c->peers) q->has_scene = false;
-    // the BVH2 is built once, on the first device; the peers derive the same arrays from it
-    bvh::Result R;
-    upload_scene(c, d, up->bvh_builder, nullptr, c->peers.empty() ? nullptr : &R);
-    for (auto& q : c->peers) {                           // replicated scene (8e)
-      upload_scene(q.get(), d, up->bvh_builder, &R, nullptr);
-      q->bvh_info = c->bvh_info;
-    }
-    HIPCHK(hipSetDevice(c->device));
-    for (auto& q : c->peers) q->has_scene = true;
-    c->has_scene = true;
-    return BLING_OK;
-  });
-}
-
-int bling_scene_upload(bling_ctx* c, const bling_scene_desc* d) {
-  const bling_upload_params up{BLING_BVH_HOST, 0u};
-  return bling_scene_upload_with(c, d, &up);
-}
-
-int bling_debug_bvh(bling_ctx* c, float* nodes, size_t cap_nodes, uint32_t* refs, size_t cap_refs, size_t* n_nodes, size_t* n_refs) {
-  return guarded([&] {
-    if (!c || !n_nodes || !n_refs) throw std::invalid_argument("null argument");
-    if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
-    *n_nodes = c->nodes.n / 4;
-    *n_refs = c->refs.n;
-    if (!nodes && !refs) return BLING_OK;
-    if ((nodes && cap_nodes < *n_nodes) || (refs && cap_refs < *n_refs)) throw std::invalid_argument("capacity below the BVH's size");
-    HIPCHK(hipSetDevice(c->device));
-    if (nodes && c->nodes.n) HIPCHK(hipMemcpy(nodes, c->nodes.p, c->nodes.n * sizeof(float4), hipMemcpyDeviceToHost));
-    if (refs && c->refs.n) HIPCHK(hipMemcpy(refs, c->refs.p, c->refs.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return BLING_OK;
-  });
-}
-
-int bling_debug_bvh_build_info(bling_ctx* c, bling_bvh_build_info* out) {
-  if (!c || !out) { g_err = "null argument"; return BLING_EINVAL; }
-  if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
-  *out = c->bvh_info;
-  return BLING_OK;
-}
-
-int bling_debug_set_bvh_depth_cap(bling_ctx* c, int cap) {
-  if (!c || cap < 0 || cap > STACK_DEPTH - 1) { g_err = "bad argument"; return BLING_EINVAL; }
-  c->bvh_depth_cap = cap;
-  return BLING_OK;
-}
-
-int bling_scene_validate(const bling_scene_desc* d) {
-  return guarded([&] {
-    validate_scene(d);
-    return BLING_OK;
-  });
-}
-
 int bling_render_pass_device(bling_ctx* c, const bling_pass_params* p, void* film, bling_stats* st) {
   return guarded([&] {
     if (!c || !p || (!film && !(p->flags & BLING_PASS_TILE_IMAGES))) throw std::invalid_argument("null argument");
@@ -1392,25 +776,6 @@ int bling_render(bling_ctx* c, const bling_pass_params* p, float* film_out, blin
     if (!report(user, &ev)) return BLING_OK;                      // PassDone ... >>= \cont -> ...
     ++pp.pass_index;
   }
-}
-
-int bling_debug_scene_info(bling_ctx* c, char* buf, size_t size, size_t* len) {
-  if (!c) { g_err = "null argument"; return BLING_EINVAL; }
-  if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_EINVAL; }
-  const DevScene& S = c->S;
-  char tmp[1024];
-  const int n = std::snprintf(tmp, sizeof tmp,
-      "{\"prims\": %u, \"bvh_depth\": %d, \"bvh_leaves\": %d, \"bvh4_nodes\": %u, \"bvh4_depth\": %d, "
-      "\"stack4_need\": %u, \"lds_all4\": %d, \"lds_trace4\": %zu, \"pkt_n\": %u, \"bf_prims\": %u, "
-      "\"features\": %u, \"stack4_lds\": %u, \"lds4_shapes\": %u, \"lds4_tris\": %u, "
-      "\"lds4_nodes\": %u, \"max_leaf\": %d, \"sample_major\": %u}",
-      c->num_prims, c->bvh_depth, c->bvh_leaves, S.num_nodes4, c->bvh4_depth, S.stack4_need, c->lds_all4 ? 1 : 0,
-      c->lds_trace4, S.pkt_n, S.bf_tris + S.bf_shapes, c->features, S.stack4_lds,
-      S.lds4_shapes, S.lds4_tris, S.lds4_nodes, c->bvh_max_leaf, S.sample_major);
-  if (n < 0) { g_err = "format error"; return BLING_EINVAL; }
-  if (len) *len = (size_t)n;
-  if (buf && size) { std::strncpy(buf, tmp, size - 1); buf[size - 1] = '\0'; }
-  return BLING_OK;
 }
 
 int bling_debug_set_mis_cull(bling_ctx* c, int on) {

@@ -18,6 +18,7 @@
 #include "../common/scene_features.h"
 #include "../common/gamma_table.h"
 #include "bvh_build.h"
+#include "scene_plan.h"
 #include "wavefront.h"
 #include "sppm.h"
 #include "light_tracer.h"
@@ -357,11 +358,11 @@ struct bling_ctx {
   // trace scratch
   DBuf<float> tr_rays, tr_t, tr_bary;
   DBuf<uint32_t> tr_prim;
-  // bvh stats
-  int bvh_depth = 0, bvh_leaves = 0, bvh_max_leaf = 0, bvh4_depth = 0;
+  // the uploaded scene's plan (scene_plan.h), as scene_upload.hip left it: the summary, and the fields the
+  // launches read
+  bplan::PlanSummary plan_info;      // bling_debug_scene_info
   bling_bvh_build_info bvh_info{};   // how the uploaded BVH2 was built (bling_debug_bvh_build_info)
   int bvh_depth_cap = 0;             // bling_debug_set_bvh_depth_cap: 0 = STACK_DEPTH - 1
-  uint32_t num_prims = 0;
   uint32_t features = FT_ALL;   // scene_features() of the uploaded scene
   size_t lds_trace = 0;         // dynamic LDS bytes of the traversal kernels
   bool lds_all = false;         // the whole BVH, triangle set and leaf refs are LDS-resident

@@ -77,7 +77,7 @@ constexpr uint32_t FT_TWO_LOBES = FT_PLASTIC | FT_GLASS | FT_TRANSMATTE | FT_SHI
 constexpr uint32_t FT_NONQUAD = FT_SPHERE | FT_SHAPES2;                // shapes other than quads
 
 constexpr uint32_t REF_TRI = 0u, REF_SHAPE = 1u, REF_FRACTAL = 2u;
-// entries - 1 of the guide table behind each Dist2D CDF on the device (core.hip, sample_c1d)
+// entries - 1 of the guide table behind each Dist2D CDF on the device (scene_plan.cpp, sample_c1d)
 constexpr int kCdfGuide = 64;
 constexpr uint32_t REF_NONE = 0xFFFFFFFFu;
 
@@ -147,7 +147,7 @@ struct DevScene {
   float inv_spp, inv_nu, inv_nv;   // 1 / (float)spp etc., rounded once on the host (binary32)
   int32_t width, height;
   int32_t ex0, ex1, ey0, ey1, ext_w;
-  // LDS plan of the traversal kernels (core.hip: plan_lds): BFS prefix of the nodes, and the whole
+  // LDS plan of the traversal kernels (scene_plan.cpp: plan_lds): BFS prefix of the nodes, and the whole
   // triangle / leaf-ref arrays when they fit, copied into dynamic LDS at block start; stack rows.
   uint32_t lds_nodes, lds_tris, lds_refs, stack_depth;
   // The same tree collapsed to 4 children per node (bvh::collapse4; 7 float4 = 112 B per node: the
@@ -160,13 +160,13 @@ struct DevScene {
   uint32_t num_nodes4, lds4_nodes, lds4_tris, lds4_refs, stack4_lds, stack4_need, stack4_lanes;
   uint32_t lds4_shapes;   // BVH4 plan: shape records 0 .. lds4_shapes - 1 copied to LDS (dev_trace.h lds_setup)
   // threaded depth-first entry list of the same BVH (bvh::threaded; 2 float4 per entry) for the
-  // wave-coherent traversal kernels, used when the scene is small (pkt_n > 0; core.hip upload)
+  // wave-coherent traversal kernels, used when the scene is small (pkt_n > 0; scene_plan.cpp scene_derive)
   gptr<float4> pkt;
   uint32_t pkt_n;
   uint32_t pkt_refs;            // leaf refs of that BVH (the packet kernels keep the first 64 in a VGPR)
   uint32_t sample_major;        // camera-sample slot order of a tile (wavefront.h k_raygen): 1 for pkt scenes
   uint32_t bf_tris, bf_shapes;  // > 0: the queue traversal kernels test every primitive (dev_trace.h
-                                // brute_walk; core.hip upload: scenes of a few dozen primitives)
+                                // brute_walk; scene_plan.cpp scene_derive: scenes of a few dozen primitives)
   // boundingSphere of the scene's worldBounds (AABB.hs:62-66; the kd-tree bounds: union of the
   // reference primitive bounds), for infinite-light photon emission (Light.hs:190-208)
   float world_c[3], world_r;

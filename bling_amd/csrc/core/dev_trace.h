@@ -51,7 +51,7 @@ constexpr bool use_bvh4() { return !(F & FT_FRACTAL); }
 //
 // The leaf-order record of leaf slot j, 3 float4 at index 3 j of DevScene::leaf_geo and of its LDS
 // copy: a triangle's {v0.xyz e1.x | e1.yz e2.xy | e2.z, ref, 0, 0}; a shape's slot is zeros and its
-// ref.  One zero record follows the last slot.  upload_scene (core.hip) is the one builder;
+// ref.  One zero record follows the last slot.  scene_derive (scene_plan.cpp) is the one builder;
 // lds_setup<..., LEAF = true> copies its output, the tests read a, b and the first half of c.
 struct LeafRec { float4 a, b; float2 c; };      // c = (e2.z, ref)
 __host__ __device__ inline uint32_t leaf_geo_quads(uint32_t n_refs) { return 3u * (n_refs + 1u); }   // float4 of all records
@@ -640,7 +640,7 @@ DEV bool leaf_hit(const LdsScene& L, const LeafRec& q, const Ray& r, HitRec& h, 
 }
 
 // The BVH4 kernels with a global fallback: leaf slot j's record from S.leaf_geo (the same records
-// in global memory, core.hip upload), so the test waits on one dependent load, not on the ref and
+// in global memory, scene_plan.cpp scene_derive), so the test waits on one dependent load, not on the ref and
 // then the triangle.  Shapes keep their records in LDS when planned there (prim_hit_ref's rule).
 template <bool ANY, uint32_t F>
 DEV bool leaf_hit_global(const DevScene& S, const LdsScene& L, uint32_t j, const Ray& r, HitRec& h, TraceCount& tc) {

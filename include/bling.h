@@ -790,6 +790,10 @@ int bling_debug_compact(bling_ctx* ctx, const uint8_t* flags, const uint32_t* qu
  * NUL-terminated into buf (at most size bytes); *len (may be NULL) receives the full length.
  * Diagnostics for bench.py and the tests; no reference counterpart. */
 int bling_debug_scene_info(bling_ctx* ctx, char* buf, size_t size, size_t* len);
+/* The same JSON object for a description that is not uploaded: the plan bling_scene_upload would settle
+ * (its host builder), from the description alone -- no context and no device, like bling_scene_validate,
+ * whose refusals it shares (BLING_EINVAL with the reason). */
+int bling_debug_scene_plan(const bling_scene_desc* desc, char* buf, size_t size, size_t* len);
 
 /* Diagnostics: the uploaded scene's BVH2 as the kernels walk it, whichever builder made it, read back from
  * device_ids[0]: 16 floats per node (two child boxes, two links, two zero words) and the leaf refs.  *n_nodes
@@ -809,7 +813,8 @@ typedef struct bling_bvh_build_info {
   uint32_t fallback;              /* BLING_BVH_FALLBACK_*: why used differs from requested */
   uint32_t items, nodes, depth, leaves, max_leaf;
   double ms_build;                /* device builder: HIP events around its kernels; host builder: wall time */
-  double ms_derive;               /* host wall time of what is derived from the BVH2: BVH4, threaded list, plans, leaf records */
+  double ms_derive;               /* host wall time of what is derived from the BVH2: BVH4, threaded list, plans, leaf records;
+                                   * host work alone (it used to span the upload of the tree's five arrays too) */
 } bling_bvh_build_info;
 int bling_debug_bvh_build_info(bling_ctx* ctx, bling_bvh_build_info* out);
 /* Test hook: the depth above which the device builder stands down, 1 .. 31; 0 restores 31. */

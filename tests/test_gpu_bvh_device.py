@@ -4,7 +4,7 @@ radiance, films, the CLI's files -- against the same scene uploaded with the hos
 
 Scenes come from tests/plan_scenes.py (no two triangles share an edge or a plane, so exact ties have
 measure zero and zero mismatches are required); the items are plan_scenes.prim_boxes and the refs
-(kind << 30 | index) in primitive order, as core.hip upload_scene forms them.
+(kind << 30 | index) in primitive order, as scene_plan.cpp scene_items forms them.
 """
 import os
 import subprocess
@@ -17,6 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import bling_amd  # noqa: E402
 import plan_scenes  # noqa: E402
+from plan_scenes import items, same_bits  # noqa: E402
 from bling_amd.render import BlingError, Context, host_camera_samples  # noqa: E402
 from bling_amd.scene import load_config, parse_job  # noqa: E402
 from scene_desc import desc  # noqa: E402
@@ -39,18 +40,6 @@ def ctx():
 @pytest.fixture(scope="module")
 def scene_dir(tmp_path_factory):
     return tmp_path_factory.mktemp("bvh_device")
-
-
-def items(job):
-    """(boxes (n, 2, 3), refs (n,)) in primitive order."""
-    d = desc(job)
-    refs = np.array([(int(d.prim_kind[i]) << 30) | int(d.prim_index[i]) for i in range(d.num_prims)], np.uint32)
-    return plan_scenes.prim_boxes(job), refs
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def cell_scene(dirname):

@@ -1,7 +1,7 @@
 """Every traversal kernel plan, on generated scenes (tests/plan_scenes.py), against the CPU oracle.
 
-The core picks its closest-hit / any-hit kernels from the scene's size and make-up alone (core.hip
-upload_scene, plan_lds, plan_lds4; core_wave.h TraceLaunch, run_wave_prof).  The shipped scenes land
+The core picks its closest-hit / any-hit kernels from the scene's size and make-up alone (scene_plan.cpp
+scene_derive, plan_lds, plan_lds4; core_wave.h TraceLaunch, run_wave_prof).  The shipped scenes land
 in three spots of that plan space; the cases here sit on its boundaries, and each one asserts its
 regime from scene_info() before it compares anything:
 
@@ -45,7 +45,10 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import bling_amd  # noqa: E402
 import plan_scenes  # noqa: E402
+from plan_scenes import CASES, FOUND, assert_regime, scan_plans  # noqa: E402
+from plan_scenes import case_scene as _build  # noqa: E402
 from bling_amd.scene import parse_job  # noqa: E402
 from oracle_py import Oracle  # noqa: E402
 from parity_util import film_errors, random_samples, report, spectra_mismatch  # noqa: E402
@@ -54,36 +57,6 @@ from test_gpu_parity import camera_rays, random_rays  # noqa: E402
 
 SEED = 0x0B11A6
 MISS = 0xFFFFFFFF
-LDS4_BUDGET = 26 * 1024          # plan_lds4's block budget
-N_H = 136                        # chain: smallest n (step 4) with bvh_depth == 31 and max_leaf > 2
-H_D0 = 1e-9                      # H's nearest triangle: 1e-9 x 1.5^135 = 6e14, squares < 3.4e38
-# triangle counts the GPU scans found (test_scans_agree_with_the_recorded_counts keeps them honest);
-# the CPU test below checks the generator at exactly these scenes
-FOUND = {"Bp": 13, "C": 14, "E": 144, "F": 145, "F2": 448, "G": 24}
-CASES = ["A", "B", "Bp", "C", "D", "E", "F", "F2", "G", "H"]
-
-
-def _build(dirname, name, n=None):
-    """(path, triangles, shapes) of a case's scene; n: the count a scan chose (else FOUND's)."""
-    n = FOUND.get(name) if n is None else n
-    if name == "A":
-        return plan_scenes.soup(dirname, 12, 4, degenerate=True), 12, 4
-    if name == "B":
-        return plan_scenes.soup(dirname, 13, 4), 13, 4
-    if name == "Bp":
-        return plan_scenes.soup(dirname, n, 4), n, 4
-    if name in ("C", "E", "F"):
-        return plan_scenes.soup(dirname, n, 4, degenerate=True), n, 4
-    if name == "D":
-        return plan_scenes.soup(dirname, 40, 9), 40, 9
-    if name == "F2":
-        return plan_scenes.soup(dirname, n, 4), n, 4
-    if name == "G":
-        return plan_scenes.chain(dirname, n), n, 4
-    assert name == "H"
-    return plan_scenes.chain(dirname, N_H, d0=H_D0), N_H, 4
-
-
 @pytest.fixture(scope="module")
 def scene_dir(tmp_path_factory):
     return tmp_path_factory.mktemp("plan_scenes")
@@ -111,6 +84,25 @@ def test_generated_scenes_are_not_vacuous(scene_dir, name):
     assert named >= (0.6 if name in ("G", "H") else 0.75)
 
 
+# ------------------------------------------------------------------ CPU: the plan, no device
+def _plan_info(path):
+    return bling_amd.scene_plan(parse_job(path))
+
+
+def test_plan_scans_agree_with_the_recorded_counts(scene_dir, monkeypatch):
+    """The boundaries of the plan space, scanned with the device-free plan, are the recorded ones."""
+    monkeypatch.delenv("BLING_BRUTE", raising=False)
+    assert scan_plans(_plan_info, scene_dir) == FOUND
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_plan_puts_the_case_in_its_regime(scene_dir, monkeypatch, name):
+    """Every case's regime, and the 26 KiB budget of an all-LDS block, from the device-free plan."""
+    monkeypatch.delenv("BLING_BRUTE", raising=False)
+    path, nt, ns = _build(scene_dir, name)
+    assert_regime(name, nt, ns, _plan_info(path))
+
+
 # ------------------------------------------------------------------ GPU
 @pytest.fixture(scope="module")
 def ctx():
@@ -127,40 +119,7 @@ def _upload_info(ctx, path):
 @pytest.fixture(scope="module")
 def plans(ctx, scene_dir):
     """The scanned cases' triangle counts, from uploads alone: {case: n}."""
-    found = {}
-    # Bp / C: step the soup upward from 17 primitives while the packet kernels are chosen
-    n = 13
-    while _upload_info(ctx, plan_scenes.soup(scene_dir, n + 1, 4))[1]["pkt_n"] > 0 and n < 64:
-        n += 1
-    c = n + 1
-    while _upload_info(ctx, plan_scenes.soup(scene_dir, c, 4, degenerate=True))[1]["pkt_n"] > 0 and c < 64:
-        c += 1
-    found["Bp"], found["C"] = n, c
-    # E / F: steps of 8 until lds_all4 drops, then single steps inside that bracket
-    lo = 64
-    assert _upload_info(ctx, plan_scenes.soup(scene_dir, lo, 4, degenerate=True))[1]["lds_all4"] == 1
-    while lo < 320 and _upload_info(ctx, plan_scenes.soup(scene_dir, lo + 8, 4, degenerate=True))[1]["lds_all4"] == 1:
-        lo += 8
-    f = lo + 1
-    while _upload_info(ctx, plan_scenes.soup(scene_dir, f, 4, degenerate=True))[1]["lds_all4"] == 1:
-        f += 1
-    found["E"], found["F"] = f - 1, f
-    # F2: steps of 32 until the LDS node prefix no longer holds the whole BVH4
-    f2 = 320
-    while f2 < 640:
-        si = _upload_info(ctx, plan_scenes.soup(scene_dir, f2, 4))[1]
-        if si["lds4_nodes"] < si["bvh4_nodes"]:
-            break
-        f2 += 32
-    found["F2"] = f2
-    # G: chain(24), or the next n whose BVH4 stack bound exceeds the rows kept in LDS
-    g = 24
-    while g < 40:
-        si = _upload_info(ctx, plan_scenes.chain(scene_dir, g))[1]
-        if si["stack4_need"] > si["stack4_lds"]:
-            break
-        g += 1
-    found["G"] = g
+    found = scan_plans(lambda path: _upload_info(ctx, path)[1], scene_dir)
     report("traversal_plans_scan", **found)
     return found
 
@@ -176,31 +135,7 @@ def _case(ctx, scene_dir, plans, name):
     path, nt, ns = _build(scene_dir, name, plans.get(name))
     job, si = _upload_info(ctx, path)
     report(f"traversal_plan[{name}]", tris=nt, shapes=ns, **si)
-    assert si["prims"] == nt + ns
-    if name == "A":
-        assert si["bf_prims"] == 16
-    elif name in ("B", "Bp"):
-        assert si["bf_prims"] == 0 and si["pkt_n"] > 0 and si["sample_major"] == 1
-    else:
-        assert si["bf_prims"] == 0 and si["pkt_n"] == 0 and si["sample_major"] == 0
-    if name == "C":
-        assert ns <= 8 and si["lds_all4"] == 1
-    if name == "D":
-        assert si["lds_all4"] == 0 and si["lds4_shapes"] == 0 and si["lds4_tris"] == nt
-    if name == "E":
-        assert si["lds_all4"] == 1
-    if name == "F":
-        assert si["lds_all4"] == 0 and si["lds4_tris"] == 0
-    if name == "F2":
-        assert si["lds_all4"] == 0 and si["lds4_tris"] == 0 and 0 < si["lds4_nodes"] < si["bvh4_nodes"]
-    if name == "G":
-        assert si["stack4_need"] > si["stack4_lds"] and si["bvh_depth"] < 31
-    if name == "H":
-        assert si["bvh_depth"] == 31 and si["max_leaf"] > 2
-    # plan consistency: an all-LDS block stays within plan_lds4's budget at the size it launches with
-    if si["lds_all4"] == 1:
-        assert si["lds_trace4"] <= LDS4_BUDGET, si
-        assert si["stack4_lds"] == si["stack4_need"] and si["lds4_nodes"] == si["bvh4_nodes"]
+    assert_regime(name, nt, ns, si)
     return job, Oracle(job), si
 
 
