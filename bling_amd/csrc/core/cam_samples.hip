@@ -17,16 +17,15 @@ bool cam_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
   return a && b && pa < pb + nb && pb < pa + na;
 }
 
-// everything the two entry points refuse before they look at the outputs; BLING_OK: go on, *n = first[n_windows]
-int cam_ready(bling_ctx* c, const bling_image_window* windows, const uint64_t* first, size_t n_windows, uint64_t* n) {
+// everything the two entry points refuse before they look at the outputs; returns first[n_windows]
+uint64_t cam_ready(bling_ctx* c, const bling_image_window* windows, const uint64_t* first, size_t n_windows) {
   if (!c) throw std::invalid_argument("null argument");
-  if (!c->has_scene) { set_last_error("no scene uploaded"); return BLING_ENOSCENE; }
+  need_scene(c);
   std::string why;
   const bcam::Extent e{c->S.ex0, c->S.ex1, c->S.ey0, c->S.ey1};
   if (!bcam::check(c->cfg, e, windows, first, n_windows, &why)) throw std::invalid_argument(why);
   if (n_windows >= ((size_t)1 << 31)) throw std::invalid_argument("camera_samples: 2^31 windows or more");
-  *n = first[n_windows];
-  return BLING_OK;
+  return first[n_windows];
 }
 
 void cam_check_outputs(const void* xy, const void* ids, const void* rays, const void* lens, uint64_t n) {
@@ -87,8 +86,7 @@ int bling_camera_samples_device(bling_ctx* c, uint32_t seed, uint32_t pass_index
                                 const uint64_t* first, size_t n_windows, void* xy_dev, void* ids_dev, void* rays_soa_dev,
                                 void* lens_dev, bling_camera_stats* st) {
   return guarded([&] {
-    uint64_t n = 0;
-    if (int rc = cam_ready(c, windows, first, n_windows, &n)) return rc;
+    const uint64_t n = cam_ready(c, windows, first, n_windows);
     if (st) *st = bling_camera_stats{0, n_windows, 0.0};
     if (n == 0) return BLING_OK;
     cam_check_outputs(xy_dev, ids_dev, rays_soa_dev, lens_dev, n);
@@ -102,8 +100,7 @@ int bling_camera_samples(bling_ctx* c, uint32_t seed, uint32_t pass_index, const
                          const uint64_t* first, size_t n_windows, float* xy, uint32_t* ids, float* rays_soa, float* lens,
                          bling_camera_stats* st) {
   return guarded([&] {
-    uint64_t n = 0;
-    if (int rc = cam_ready(c, windows, first, n_windows, &n)) return rc;
+    const uint64_t n = cam_ready(c, windows, first, n_windows);
     if (st) *st = bling_camera_stats{0, n_windows, 0.0};
     if (n == 0) return BLING_OK;
     cam_check_outputs(xy, ids, rays_soa, lens, n);

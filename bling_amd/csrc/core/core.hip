@@ -7,9 +7,9 @@
 //   k_film            per-tile filtered splat into LDS + merge into the film (Image.hs:108-299)
 // Path state is SoA (one 64-B record per spectrum) indexed through compacted queues.  Traversal
 // uses the LDS stack of dev_trace.h.
-// This unit holds the pass driver, the film, tile and develop calls, bling_render, the debug and trace
-// calls and the SPPM, light tracer and Metropolis entries.  What a scene becomes before a pass is planned
-// on the host in scene_plan.cpp and put on the devices by scene_upload.hip.
+// This unit holds the pass driver, the film, tile and develop calls, bling_render and the debug and trace
+// calls.  What a scene becomes before a pass is planned on the host in scene_plan.cpp and put on the devices
+// by scene_upload.hip; the SPPM, light tracer and Metropolis entries are in splat_renderers.hip.
 #include "core_internal.h"
 #include "pass_plan.h"
 #include "pass_stats.h"
@@ -486,7 +486,7 @@ int bling_create(const int* device_ids, int n_devices, bling_ctx** out) {
 int bling_render_pass_device(bling_ctx* c, const bling_pass_params* p, void* film, bling_stats* st) {
   return guarded([&] {
     if (!c || !p || (!film && !(p->flags & BLING_PASS_TILE_IMAGES))) throw std::invalid_argument("null argument");
-    if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
+    need_scene(c);
     HIPCHK(hipSetDevice(c->device));
     return render_fanout(c, p, static_cast<float*>(film), st);
   });
@@ -495,14 +495,12 @@ int bling_render_pass_device(bling_ctx* c, const bling_pass_params* p, void* fil
 int bling_render_pass(bling_ctx* c, const bling_pass_params* p, float* film_out, bling_stats* st) {
   return guarded([&] {
     if (!c || !p) throw std::invalid_argument("null argument");
-    if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
+    need_scene(c);
     HIPCHK(hipSetDevice(c->device));
-    size_t n = (size_t)c->S.width * c->S.height * 4;
-    if (c->film_dev.n != n) c->film_dev.alloc(n);
-    if (film_out) HIPCHK(hipMemcpy(c->film_dev.p, film_out, n * sizeof(float), hipMemcpyHostToDevice));
-    else HIPCHK(hipMemset(c->film_dev.p, 0, n * sizeof(float)));
-    int rc = render_fanout(c, p, c->film_dev.p, st);
-    if (rc == BLING_OK && film_out) HIPCHK(hipMemcpy(film_out, c->film_dev.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    const size_t n = (size_t)c->S.width * c->S.height * 4;
+    stage_in(c->film_dev, film_out, n);
+    const int rc = render_fanout(c, p, c->film_dev.p, st);
+    if (rc == BLING_OK) stage_out(film_out, c->film_dev, n);
     return rc;
   });
 }
@@ -511,7 +509,7 @@ static int sample_li_impl(bling_ctx* c, uint32_t seed, uint32_t pass_index, cons
                    float* img_out, bling_stats* st, float* vtx_out, float* terms_out = nullptr, int32_t* lens_out = nullptr) {
   return guarded([&] {
     if (!c || !samples || !L_out) throw std::invalid_argument("null argument");
-    if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
+    need_scene(c);
     if (n == 0) return BLING_OK;
     if (n > (1u << 24)) throw std::invalid_argument("too many samples");
     HIPCHK(hipSetDevice(c->device));
@@ -573,7 +571,7 @@ int bling_pass_tile_layout(bling_ctx* c, const bling_pass_params* p, int32_t* or
                            int32_t* slot_w, int32_t* slot_h) {
   return guarded([&] {
     if (!c || !p || !n_tiles) throw std::invalid_argument("null argument");
-    if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
+    need_scene(c);
     const std::vector<TileDesc> tiles = pass_tiles(c->S, p->shard_rank, p->shard_world, p->tile_stride);
     *n_tiles = tiles.size();
     int sw, sh;
@@ -601,7 +599,7 @@ static void check_tiles_capacity(bling_ctx* c, const bling_pass_params* p, size_
 int bling_film_add_tiles(bling_ctx* c, const bling_pass_params* p, const void* tiles_device, void* film_device) {
   return guarded([&] {
     if (!c || !p || !tiles_device || !film_device) throw std::invalid_argument("null argument");
-    if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
+    need_scene(c);
     HIPCHK(hipSetDevice(c->device));
     const std::vector<TileDesc> tiles = pass_tiles(c->S, p->shard_rank, p->shard_world, p->tile_stride);
     check_tiles_capacity(c, p, tiles.size());
@@ -618,7 +616,7 @@ int bling_film_add_tiles(bling_ctx* c, const bling_pass_params* p, const void* t
 int bling_film_add_shards(bling_ctx* c, const bling_pass_params* p, const void* const* tiles_devices, void* film_device) {
   return guarded([&] {
     if (!c || !p || !tiles_devices || !film_device) throw std::invalid_argument("null argument");
-    if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
+    need_scene(c);
     HIPCHK(hipSetDevice(c->device));
     const int world = std::max(1, p->shard_world);
     std::vector<std::vector<TileDesc>> tiles(world);
@@ -644,13 +642,12 @@ int bling_film_add_shards(bling_ctx* c, const bling_pass_params* p, const void* 
 }
 
 namespace {
-// the checks the two develop calls share; BLING_OK, or the error with g_err set
-int develop_check(bling_ctx* c, const bling_develop_params* dp, const void* film, const void* out) {
+// the checks the two develop calls share
+void develop_check(bling_ctx* c, const bling_develop_params* dp, const void* film, const void* out) {
   if (!c || !dp || !film || !out) throw std::invalid_argument("null argument");
-  if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
+  need_scene(c);
   if (dp->format != BLING_DEVELOP_RGB_F32 && dp->format != BLING_DEVELOP_RGB8 && dp->format != BLING_DEVELOP_RGBE)
     throw std::invalid_argument("develop: unknown format " + std::to_string(dp->format));
-  return BLING_OK;
 }
 bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
   const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
@@ -660,7 +657,7 @@ bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
 
 int bling_film_develop_device(bling_ctx* c, const bling_develop_params* dp, const void* film, const void* splat, void* out) {
   return guarded([&] {
-    if (int rc = develop_check(c, dp, film, out)) return rc;
+    develop_check(c, dp, film, out);
     const size_t px = (size_t)c->S.width * c->S.height, nout = px * develop_pixel_bytes(dp->format);
     if (ranges_overlap(out, nout, film, px * 16) || (splat && ranges_overlap(out, nout, splat, px * 12)))
       throw std::invalid_argument("develop: out overlaps the film or the splat buffer");
@@ -673,9 +670,9 @@ int bling_film_develop_device(bling_ctx* c, const bling_develop_params* dp, cons
 
 int bling_film_develop(bling_ctx* c, const bling_develop_params* dp, const float* film, const float* splat, void* out) {
   return guarded([&] {
-    if (int rc = develop_check(c, dp, film, out)) return rc;
+    develop_check(c, dp, film, out);
     int x0, x1, y0, y1;
-    if (!develop_clip(c, dp->window, &x0, &x1, &y0, &y1)) return (int)BLING_OK;   // nothing to write
+    if (!develop_clip(c, dp->window, &x0, &x1, &y0, &y1)) return BLING_OK;   // nothing to write
     HIPCHK(hipSetDevice(c->device));
     const size_t w = (size_t)c->S.width, px = w * c->S.height, bpp = develop_pixel_bytes(dp->format);
     if (c->film_dev.n != px * 4) c->film_dev.alloc(px * 4);
@@ -705,7 +702,7 @@ namespace {
 int region_pass(bling_ctx* c, const bling_pass_params& p, bling_stats* st, std::vector<TileDesc>& tiles,
                 std::vector<float>& images, int& sw, int& sh) {
   return guarded([&] {
-    if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
+    need_scene(c);
     HIPCHK(hipSetDevice(c->device));
     tiles = pass_tiles(c->S, p.shard_rank, p.shard_world, p.tile_stride);
     tile_slot(c->S, &sw, &sh);
@@ -886,7 +883,7 @@ int bling_sample_li_vertices(bling_ctx* c, uint32_t seed, uint32_t pass_index, c
 int bling_trace(bling_ctx* c, const float* rays, size_t n, int any_hit, float* t_out, uint32_t* prim_out, float* bary_out) {
   return guarded([&] {
     if (!c || !rays || !prim_out) throw std::invalid_argument("null argument");
-    if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
+    need_scene(c);
     if (n == 0) return BLING_OK;
     HIPCHK(hipSetDevice(c->device));
     c->tr_rays.upload(rays, 8 * n);
@@ -906,7 +903,7 @@ int bling_trace_device(bling_ctx* c, const void* rays, size_t n, int any_hit, vo
                        int repeats, double* ms_out) {
   return guarded([&] {
     if (!c || !rays || !prim_dev) throw std::invalid_argument("null argument");
-    if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
+    need_scene(c);
     HIPCHK(hipSetDevice(c->device));
     const EventPair ev;
     ev.a.record(c->stream);
@@ -917,415 +914,6 @@ int bling_trace_device(bling_ctx* c, const void* rays, size_t n, int any_hit, vo
     ev.b.record(c->stream);
     HIPCHK(hipEventSynchronize(ev.b));
     if (ms_out) *ms_out = ev.elapsed_ms() / std::max(1, repeats);
-    return BLING_OK;
-  });
-}
-
-static int sppm_ready(bling_ctx* c) {
-  if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
-  if (c->cfg.renderer != BLING_RENDERER_SPPM) throw std::invalid_argument("the uploaded scene's renderer is not sppm");
-  if (c->features & FT_PROCTEX) {
-    g_err = "sppm: blend / gradient / checker / cellNoise textures are not supported by the SPPM renderer";
-    return BLING_EUNSUPPORTED;
-  }
-  return BLING_OK;
-}
-
-static void sppm_launch(bling_ctx* c, uint32_t seed, uint32_t pass, float* film, float* splat, uint32_t flags, bling_sppm_stats* st) {
-  if ((c->features & ~kProfiles[0]) == 0u) sppm_pass_t<kProfiles[0]>(c, seed, pass, film, splat, flags, st);
-  else sppm_pass_t<kSppmAll>(c, seed, pass, film, splat, flags, st);
-}
-
-int bling_sppm_pass(bling_ctx* c, uint32_t seed, uint32_t pass_index, float* film_out, float* splat_out,
-                    bling_sppm_stats* st) {
-  return guarded([&] {
-    if (!c) throw std::invalid_argument("null argument");
-    if (int rc = sppm_ready(c)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    if (!c->sppm.ready) sppm_init(c);
-    SppmState& P = c->sppm;
-    const size_t nf = (size_t)c->S.width * c->S.height * 4, ns = (size_t)c->S.width * c->S.height * 3;
-    if (film_out) HIPCHK(hipMemcpy(P.film.p, film_out, nf * sizeof(float), hipMemcpyHostToDevice));
-    else HIPCHK(hipMemset(P.film.p, 0, nf * sizeof(float)));
-    if (splat_out) HIPCHK(hipMemcpy(P.splat.p, splat_out, ns * sizeof(float), hipMemcpyHostToDevice));
-    else HIPCHK(hipMemset(P.splat.p, 0, ns * sizeof(float)));
-    if (st) std::memset(st, 0, sizeof *st);
-    sppm_launch(c, seed, pass_index, P.film.p, P.splat.p, 0u, st);
-    if (film_out) HIPCHK(hipMemcpy(film_out, P.film.p, nf * sizeof(float), hipMemcpyDeviceToHost));
-    if (splat_out) HIPCHK(hipMemcpy(splat_out, P.splat.p, ns * sizeof(float), hipMemcpyDeviceToHost));
-    return (int)BLING_OK;
-  });
-}
-
-int bling_sppm_pass_device(bling_ctx* c, uint32_t seed, uint32_t pass_index, uint32_t flags, void* film_device, void* splat_device,
-                           bling_sppm_stats* st) {
-  return guarded([&] {
-    if (!c) throw std::invalid_argument("null argument");
-    if (flags & ~BLING_SPLAT_ORDERED) throw std::invalid_argument("unknown splat flag bits " + std::to_string(flags & ~BLING_SPLAT_ORDERED));
-    if (int rc = sppm_ready(c)) return rc;
-    if (!c->peers.empty()) throw std::invalid_argument("bling_sppm_pass_device runs on a single-device context");
-    HIPCHK(hipSetDevice(c->device));
-    if (!c->sppm.ready) sppm_init(c);
-    if (st) std::memset(st, 0, sizeof *st);
-    sppm_launch(c, seed, pass_index, static_cast<float*>(film_device), static_cast<float*>(splat_device), flags, st);
-    return (int)BLING_OK;
-  });
-}
-
-int bling_debug_sppm_records(bling_ctx* c, uint32_t seed, uint32_t pass_index, uint32_t thread, uint32_t first_photon,
-                             uint32_t n_photons, bling_sppm_record* records, size_t cap, size_t* n) {
-  return guarded([&] {
-    if (!c || !n || (cap && !records)) throw std::invalid_argument("null argument");
-    *n = 0;
-    if (int rc = sppm_ready(c)) return rc;
-    if (!c->peers.empty()) throw std::invalid_argument("bling_debug_sppm_records runs on a single-device context");
-    const uint32_t sn = sppm_sn(c);
-    if (thread >= (uint32_t)std::max(1, c->cfg.sppm_threads)) throw std::invalid_argument("sampler beyond sppm_threads");
-    if ((uint64_t)first_photon + n_photons > (uint64_t)sn * sn) throw std::invalid_argument("photon range beyond the sampler's sn^2");
-    if (cap > 0x7FFFFFFFull) throw std::invalid_argument("record capacity too large");
-    if (n_photons == 0) return (int)BLING_OK;
-    HIPCHK(hipSetDevice(c->device));
-    if (!c->sppm.ready) sppm_init(c);
-    // a launch needs a buffer to claim slots in: one record at least, so the count is always known
-    const uint32_t rcap = (uint32_t)std::max<size_t>(cap, 1);
-    const uint32_t got = (c->features & ~kProfiles[0]) == 0u
-                             ? sppm_records_t<kProfiles[0]>(c, seed, pass_index, thread, first_photon, n_photons, rcap)
-                             : sppm_records_t<kSppmAll>(c, seed, pass_index, thread, first_photon, n_photons, rcap);
-    *n = got;
-    if (got > cap) {
-      g_err = "sppm records: " + std::to_string(got) + " records exceed the capacity " + std::to_string(cap);
-      return (int)BLING_EINVAL;
-    }
-    std::vector<uint4> raw((size_t)2 * got);
-    if (got) HIPCHK(hipMemcpy(raw.data(), c->sppm.rec.p, raw.size() * sizeof(uint4), hipMemcpyDeviceToHost));
-    const uint32_t W = (uint32_t)c->S.width;
-    for (uint32_t i = 0; i < got; ++i) {
-      const uint4 a = raw[2 * (size_t)i], b = raw[2 * (size_t)i + 1];
-      bling_sppm_record& r = records[i];
-      r.thread = thread; r.photon = a.w; r.seq = a.z; r.depth = a.y;
-      r.sx = (int32_t)(a.x % W); r.sy = (int32_t)(a.x / W);
-      std::memcpy(&r.x, &b.x, 3 * sizeof(float));
-      r.pad = 0u;
-    }
-    std::sort(records, records + got, [](const bling_sppm_record& p, const bling_sppm_record& q) {
-      return p.photon != q.photon ? p.photon < q.photon : p.seq < q.seq;
-    });
-    return (int)BLING_OK;
-  });
-}
-
-int bling_sppm_pixel_stats(bling_ctx* c, float* r2_out, float* n_out, size_t* n_pixels) {
-  return guarded([&] {
-    if (!c) throw std::invalid_argument("null argument");
-    if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
-    if (c->cfg.renderer != BLING_RENDERER_SPPM) throw std::invalid_argument("the uploaded scene's renderer is not sppm");
-    if (c->features & FT_PROCTEX) {
-      g_err = "sppm: blend / gradient / checker / cellNoise textures are not supported by the SPPM renderer";
-      return BLING_EUNSUPPORTED;
-    }
-    HIPCHK(hipSetDevice(c->device));
-    if (!c->sppm.ready) sppm_init(c);
-    SppmState& P = c->sppm;
-    if (n_pixels) *n_pixels = P.n_stats;
-    if (r2_out) HIPCHK(hipMemcpy(r2_out, P.r2.p, P.n_stats * sizeof(float), hipMemcpyDeviceToHost));
-    if (n_out) HIPCHK(hipMemcpy(n_out, P.nacc.p, P.n_stats * sizeof(float), hipMemcpyDeviceToHost));
-    return BLING_OK;
-  });
-}
-
-int bling_debug_sppm_hitpoints(bling_ctx* c, float* pos_r2, uint64_t* keys, size_t cap, size_t* n) {
-  return guarded([&] {
-    if (!c) throw std::invalid_argument("null argument");
-    if (!c->sppm.ready) { g_err = "no SPPM pass has run"; return BLING_EINVAL; }
-    HIPCHK(hipSetDevice(c->device));
-    SppmState& P = c->sppm;
-    uint32_t cnt = 0;
-    HIPCHK(hipMemcpy(&cnt, P.hp_count.p, sizeof cnt, hipMemcpyDeviceToHost));
-    const size_t m = std::min<size_t>(cnt, P.hp_cap);
-    if (n) *n = m;
-    const size_t k = std::min(m, cap);
-    if (pos_r2 && k) HIPCHK(hipMemcpy(pos_r2, P.hp_pos.p, k * sizeof(float4), hipMemcpyDeviceToHost));
-    if (keys && k) HIPCHK(hipMemcpy(keys, P.hp_key.p, k * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return BLING_OK;
-  });
-}
-
-int bling_debug_sppm_buckets(bling_ctx* c, uint32_t* bstart, uint32_t* items, float* mr, size_t cap_b, size_t cap_i,
-                             size_t* nb, size_t* ni) {
-  return guarded([&] {
-    if (!c) throw std::invalid_argument("null argument");
-    if (!c->sppm.ready) { g_err = "no SPPM pass has run"; return BLING_EINVAL; }
-    HIPCHK(hipSetDevice(c->device));
-    SppmState& P = c->sppm;
-    SppmGrid g;
-    HIPCHK(hipMemcpy(&g, P.grid.p, sizeof g, hipMemcpyDeviceToHost));
-    if (nb) *nb = (size_t)g.cnt + 1;
-    if (ni) *ni = g.items;
-    if (bstart && cap_b >= (size_t)g.cnt + 1) HIPCHK(hipMemcpy(bstart, P.bstart.p, ((size_t)g.cnt + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (items && cap_i >= g.items && g.items) HIPCHK(hipMemcpy(items, P.items.p, (size_t)g.items * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (mr && cap_i >= g.items && g.items) HIPCHK(hipMemcpy(mr, P.kd_mr.p, (size_t)g.items * sizeof(float), hipMemcpyDeviceToHost));
-    return BLING_OK;
-  });
-}
-
-int bling_sppm_reset(bling_ctx* c) {
-  return guarded([&] {
-    if (!c) throw std::invalid_argument("null argument");
-    HIPCHK(hipSetDevice(c->device));
-    c->sppm.free_all();
-    return BLING_OK;
-  });
-}
-
-// ---- light tracer (light_tracer.h, light_pass.hip)
-static int light_ready(bling_ctx* c) {
-  if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
-  if (c->cfg.renderer != BLING_RENDERER_LIGHT) throw std::invalid_argument("the uploaded scene's renderer is not the light tracer");
-  if (!c->peers.empty()) throw std::invalid_argument("the light tracer runs on a single-device context");
-  if (c->S.camera.kind != BLING_CAM_PERSPECTIVE) {
-    g_err = "light tracer: an environment camera cannot be sampled (sampleCam, Camera.hs:102)";
-    return BLING_EUNSUPPORTED;
-  }
-  if (c->features & FT_PROCTEX) {
-    g_err = "light tracer: blend / gradient / checker / cellNoise textures are not supported by the light tracer";
-    return BLING_EUNSUPPORTED;
-  }
-  return BLING_OK;
-}
-
-static uint32_t light_launch(bling_ctx* c, uint32_t seed, uint32_t pass, uint32_t first, uint32_t count, float* splat,
-                             uint32_t rec_cap, bling_light_stats* st) {
-  if ((c->features & ~kProfiles[0]) == 0u) return light_pass_t<kProfiles[0]>(c, seed, pass, first, count, splat, rec_cap, st);
-  return light_pass_t<kSppmAll>(c, seed, pass, first, count, splat, rec_cap, st);
-}
-
-int bling_light_pass(bling_ctx* c, uint32_t seed, uint32_t pass_index, float* splat_inout, bling_light_stats* st) {
-  return guarded([&] {
-    if (!c) throw std::invalid_argument("null argument");
-    if (int rc = light_ready(c)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    LightState& P = c->light;
-    const size_t ns = (size_t)c->S.width * c->S.height * 3;
-    if (P.splat.n != ns) P.splat.alloc(ns);
-    if (splat_inout) HIPCHK(hipMemcpy(P.splat.p, splat_inout, ns * sizeof(float), hipMemcpyHostToDevice));
-    else HIPCHK(hipMemset(P.splat.p, 0, ns * sizeof(float)));
-    if (st) std::memset(st, 0, sizeof *st);
-    light_launch(c, seed, pass_index, 0u, (uint32_t)c->lt.pass_photons, P.splat.p, 0u, st);
-    if (splat_inout) HIPCHK(hipMemcpy(splat_inout, P.splat.p, ns * sizeof(float), hipMemcpyDeviceToHost));
-    return BLING_OK;
-  });
-}
-
-int bling_debug_light_records(bling_ctx* c, uint32_t seed, uint32_t pass_index, uint32_t first_photon, uint32_t n_photons,
-                              bling_light_record* records, size_t cap, size_t* n) {
-  return guarded([&] {
-    if (!c || !n || (cap && !records)) throw std::invalid_argument("null argument");
-    *n = 0;
-    if (int rc = light_ready(c)) return rc;
-    if ((uint64_t)first_photon + n_photons > (uint64_t)c->lt.pass_photons) throw std::invalid_argument("photon range beyond passPhotons");
-    if (cap > 0x7FFFFFFFull) throw std::invalid_argument("record capacity too large");
-    if (n_photons == 0) return BLING_OK;
-    HIPCHK(hipSetDevice(c->device));
-    // a launch needs a buffer to claim slots in: one record at least, so the count is always known
-    const uint32_t rcap = (uint32_t)std::max<size_t>(cap, 1);
-    const uint32_t got = light_launch(c, seed, pass_index, first_photon, n_photons, nullptr, rcap, nullptr);
-    *n = got;
-    if (got > cap) {
-      g_err = "light records: " + std::to_string(got) + " records exceed the capacity " + std::to_string(cap);
-      return BLING_EINVAL;
-    }
-    static_assert(sizeof(bling_light_record) == 2 * sizeof(uint4), "record layout");
-    if (got) HIPCHK(hipMemcpy(records, c->light.rec.p, (size_t)got * sizeof(bling_light_record), hipMemcpyDeviceToHost));
-    std::sort(records, records + got, [](const bling_light_record& a, const bling_light_record& b) {
-      return a.photon != b.photon ? a.photon < b.photon : a.depth < b.depth;
-    });
-    return BLING_OK;
-  });
-}
-
-// ---- Metropolis renderer (mlt.h, mlt_pass.hip)
-static int mlt_ready(bling_ctx* c) {
-  if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
-  if (c->cfg.renderer != BLING_RENDERER_METROPOLIS) throw std::invalid_argument("the uploaded scene's renderer is not metropolis");
-  if (!c->peers.empty()) throw std::invalid_argument("the Metropolis renderer runs on a single-device context");
-  return BLING_OK;
-}
-
-int bling_mlt_pass(bling_ctx* c, uint32_t seed, uint32_t pass_index, float* splat_inout, bling_mlt_stats* st) {
-  return guarded([&] {
-    if (!c) throw std::invalid_argument("null argument");
-    if (int rc = mlt_ready(c)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    LightState& P = c->light;
-    const size_t ns = (size_t)c->S.width * c->S.height * 3;
-    if (P.splat.n != ns) P.splat.alloc(ns);
-    if (splat_inout) HIPCHK(hipMemcpy(P.splat.p, splat_inout, ns * sizeof(float), hipMemcpyHostToDevice));
-    else HIPCHK(hipMemset(P.splat.p, 0, ns * sizeof(float)));
-    if (st) std::memset(st, 0, sizeof *st);
-    mlt_pass_run(c, seed, pass_index, P.splat.p, false, 0u, 0u, st, nullptr);
-    if (splat_inout) HIPCHK(hipMemcpy(splat_inout, P.splat.p, ns * sizeof(float), hipMemcpyDeviceToHost));
-    return BLING_OK;
-  });
-}
-
-int bling_debug_mlt_records(bling_ctx* c, uint32_t seed, uint32_t pass_index, uint32_t first_chain, uint32_t n_chains,
-                            bling_mlt_record* records, size_t cap, size_t* n, uint32_t* starts, float* b) {
-  return guarded([&] {
-    if (!c || !n || (cap && !records)) throw std::invalid_argument("null argument");
-    *n = 0;
-    if (int rc = mlt_ready(c)) return rc;
-    const uint64_t C = (uint64_t)c->mp.chains;
-    if ((uint64_t)first_chain + n_chains > C) throw std::invalid_argument("chain range beyond chains");
-    if (n_chains == 0) return BLING_OK;
-    const uint64_t M = (uint64_t)mlt_mutations(c->mp, c->S.width, c->S.height);
-    uint64_t need = 0;
-    for (uint64_t k = first_chain; k < (uint64_t)first_chain + n_chains; ++k) need += M / C + (k < M % C ? 1 : 0);
-    *n = (size_t)need;
-    if (need > cap) {
-      g_err = "mlt records: " + std::to_string(need) + " records exceed the capacity " + std::to_string(cap);
-      return BLING_EINVAL;
-    }
-    HIPCHK(hipSetDevice(c->device));
-    MltOut out;
-    mlt_pass_run(c, seed, pass_index, nullptr, false, first_chain, n_chains, nullptr, &out);
-    if (out.rec.size() != need) throw std::runtime_error("mlt records: count mismatch");
-    if (need) std::memcpy(records, out.rec.data(), need * sizeof(bling_mlt_record));
-    if (starts) std::memcpy(starts, out.start.data() + first_chain, (size_t)n_chains * sizeof(uint32_t));
-    if (b) *b = out.b;
-    return BLING_OK;
-  });
-}
-
-int bling_debug_mlt_boot(const float* I, uint32_t n, uint32_t seed, uint32_t pass_index, uint32_t chains, float* b,
-                         uint32_t* starts) {
-  return guarded([&] {
-    if (!I || !b || !starts || n < 1 || chains < 1) throw std::invalid_argument("null argument");
-    *b = mlt_boot_select(I, n, seed, pass_index, chains, starts);
-    return BLING_OK;
-  });
-}
-
-int bling_debug_mlt_set_boot(bling_ctx* c, const float* I, uint32_t n) {
-  return guarded([&] {
-    if (!c || (n && !I)) throw std::invalid_argument("null argument");
-    c->mlt_boot_override.assign(I, I + n);
-    return BLING_OK;
-  });
-}
-
-// ---- ordered splat films and caller-owned device splat images (splat_merge.h)
-static void splat_device_args(uint32_t flags, const void* splat_device) {
-  if (flags & ~BLING_SPLAT_ORDERED) throw std::invalid_argument("unknown splat flag bits " + std::to_string(flags & ~BLING_SPLAT_ORDERED));
-  if (!splat_device) throw std::invalid_argument("null splat_device");
-}
-
-// The ordered light tracer pass: k_lt_photon in record mode over ascending photon ranges, each merged before
-// the next.  A range whose records exceed the buffer is run again with a buffer that holds them, or, beyond
-// the budget, as two halves; nothing of it is merged before it fits.
-static int light_pass_ordered(bling_ctx* c, uint32_t seed, uint32_t pass, float* img, bling_light_stats* st) {
-  const uint32_t total = (uint32_t)c->lt.pass_photons;
-  const size_t budget = std::min<size_t>(splat_budget(c), 0x7FFFFFFFull);
-  uint32_t cap = (uint32_t)std::min<size_t>(budget, std::max<size_t>(c->light.rec.n / 2, (size_t)4 * total + 1024));
-  bling_light_stats sum{};
-  std::vector<EventPair> merges;
-  double ms_kernel = 0.;
-  uint32_t first = 0, len = total;
-  while (first < total) {
-    const uint32_t count = std::min(len, total - first);
-    bling_light_stats one{};
-    const uint32_t got = light_launch(c, seed, pass, first, count, nullptr, cap, &one);
-    ms_kernel += one.ms_total;
-    if (got > cap) {
-      if ((size_t)got <= budget) { cap = got; continue; }              // the same range, into a buffer that holds it
-      if (count == 1) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        g_err = "light tracer: photon " + std::to_string(first) + " alone writes " + std::to_string(got) +
-                " splat records, more than the record budget " + std::to_string(budget);
-        return BLING_EINVAL;
-      }
-      len = (count + 1) / 2;
-      continue;
-    }
-    merges.emplace_back();
-    merges.back().a.record(c->stream);
-    splat_merge(c, c->light.rec.p, got, SM_LAYOUT_LIGHT, img);
-    merges.back().b.record(c->stream);
-    sum.photon_rays += one.photon_rays; sum.shadow_rays += one.shadow_rays; sum.splats += one.splats; sum.dropped += one.dropped;
-    first += count;
-  }
-  HIPCHK(hipStreamSynchronize(c->stream));
-  double ms_merge = 0.;
-  for (const EventPair& p : merges) ms_merge += p.elapsed_ms();
-  c->merge.ms_kernel = ms_kernel; c->merge.ms_merge = ms_merge;
-  if (st) {
-    *st = sum;
-    st->photons = total;
-    st->ms_total = ms_kernel + ms_merge;
-  }
-  return BLING_OK;
-}
-
-int bling_light_pass_device(bling_ctx* c, uint32_t seed, uint32_t pass_index, uint32_t flags, void* splat_device,
-                            bling_light_stats* st) {
-  return guarded([&] {
-    if (!c) throw std::invalid_argument("null argument");
-    splat_device_args(flags, splat_device);
-    if (int rc = light_ready(c)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    if (st) std::memset(st, 0, sizeof *st);
-    float* img = static_cast<float*>(splat_device);
-    if (flags & BLING_SPLAT_ORDERED) return light_pass_ordered(c, seed, pass_index, img, st);
-    light_launch(c, seed, pass_index, 0u, (uint32_t)c->lt.pass_photons, img, 0u, st);
-    return (int)BLING_OK;
-  });
-}
-
-int bling_mlt_pass_device(bling_ctx* c, uint32_t seed, uint32_t pass_index, uint32_t flags, void* splat_device,
-                          bling_mlt_stats* st) {
-  return guarded([&] {
-    if (!c) throw std::invalid_argument("null argument");
-    splat_device_args(flags, splat_device);
-    if (int rc = mlt_ready(c)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    if (st) std::memset(st, 0, sizeof *st);
-    mlt_pass_run(c, seed, pass_index, static_cast<float*>(splat_device), (flags & BLING_SPLAT_ORDERED) != 0u, 0u, 0u, st, nullptr);
-    return BLING_OK;
-  });
-}
-
-int bling_debug_splat_merge(bling_ctx* c, const bling_splat_rec* recs, size_t n, void* splat_device) {
-  return guarded([&] {
-    if (!c || !splat_device || (n && !recs)) throw std::invalid_argument("null argument");
-    if (!c->has_scene) { g_err = "no scene uploaded"; return BLING_ENOSCENE; }
-    if (n > 0x7FFFFFFFull) throw std::invalid_argument("splat merge: more than 2^31 - 1 records");
-    const size_t npix = (size_t)c->S.width * c->S.height;
-    for (size_t i = 0; i < n; ++i)
-      if (recs[i].pixel >= npix) throw std::invalid_argument("splat merge: record " + std::to_string(i) + " names pixel " +
-                                                             std::to_string(recs[i].pixel) + " of " + std::to_string(npix));
-    if (n == 0) return BLING_OK;
-    HIPCHK(hipSetDevice(c->device));
-    static_assert(sizeof(bling_splat_rec) == 2 * sizeof(uint4), "record layout");
-    MergeState& G = c->merge;
-    if (G.rec.n < 2 * n) G.rec.alloc(2 * n);
-    HIPCHK(hipMemcpyAsync(G.rec.p, recs, n * sizeof(bling_splat_rec), hipMemcpyHostToDevice, c->stream));
-    splat_merge(c, G.rec.p, n, SM_LAYOUT_SPLAT, static_cast<float*>(splat_device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return BLING_OK;
-  });
-}
-
-int bling_debug_set_splat_budget(bling_ctx* c, size_t max_records) {
-  return guarded([&] {
-    if (!c) throw std::invalid_argument("null argument");
-    c->merge.budget = max_records;
-    return BLING_OK;
-  });
-}
-
-int bling_debug_splat_times(bling_ctx* c, double* ms_kernel, double* ms_merge) {
-  return guarded([&] {
-    if (!c || !ms_kernel || !ms_merge) throw std::invalid_argument("null argument");
-    *ms_kernel = c->merge.ms_kernel; *ms_merge = c->merge.ms_merge;
     return BLING_OK;
   });
 }

@@ -30,6 +30,11 @@ namespace bcore {
 using namespace bd;
 
 struct HipError : std::runtime_error { using std::runtime_error::runtime_error; };
+// An entry point's refusal under a BLING_E* code of its own (guarded returns it; any other exception is BLING_EINVAL)
+struct Refusal : std::runtime_error {
+  int code;
+  Refusal(int code, const std::string& msg) : std::runtime_error(msg), code(code) {}
+};
 
 #define HIPCHK(x)                                                                        \
   do {                                                                                   \
@@ -230,6 +235,9 @@ template <class F>
 int guarded(F f) {
   try {
     return f();
+  } catch (const Refusal& e) {
+    set_last_error(e.what());
+    return e.code;
   } catch (const HipError& e) {
     set_last_error(e.what());
     return BLING_EHIP;
@@ -514,6 +522,24 @@ struct bling_ctx {
 };
 
 namespace bcore {
+
+// what every entry point that needs the uploaded scene checks first
+inline void need_scene(const bling_ctx* c) {
+  if (!c->has_scene) throw Refusal(BLING_ENOSCENE, "no scene uploaded");
+}
+
+// Host staging of a caller's image of n elements around a pass: the caller's values (host == nullptr: zeros)
+// into buf, and back into host when there is one
+template <class T>
+void stage_in(DBuf<T>& buf, const T* host, size_t n) {
+  if (buf.n != n) buf.alloc(n);
+  if (host) HIPCHK(hipMemcpy(buf.p, host, n * sizeof(T), hipMemcpyHostToDevice));
+  else HIPCHK(hipMemset(buf.p, 0, n * sizeof(T)));
+}
+template <class T>
+void stage_out(T* host, const DBuf<T>& buf, size_t n) {
+  if (host) HIPCHK(hipMemcpy(host, buf.p, n * sizeof(T), hipMemcpyDeviceToHost));
+}
 
 // Kernel profiles: feature sets the kernels are compiled for.  A scene runs on the first profile
 // that covers its features (scene_features.h); the last one covers everything.

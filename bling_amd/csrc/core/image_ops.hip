@@ -620,7 +620,7 @@ int bling_image_add_samples_device(bling_ctx* c, const bling_image_desc* d, int 
   return guarded([&] {
     check_add(c, d, op, xy, spectra, n, target);
     add_samples(c, d, op, static_cast<const float*>(xy), static_cast<const float*>(spectra), n, static_cast<float*>(target), st);
-    return (int)BLING_OK;
+    return BLING_OK;
   });
 }
 
@@ -628,7 +628,7 @@ int bling_image_add_samples(bling_ctx* c, const bling_image_desc* d, int op, con
                             float* target, bling_image_stats* st) {
   return guarded([&] {
     check_add(c, d, op, xy, spectra, n, target);
-    if (n == 0) { add_samples(c, d, op, nullptr, nullptr, 0, nullptr, st); return (int)BLING_OK; }
+    if (n == 0) { add_samples(c, d, op, nullptr, nullptr, 0, nullptr, st); return BLING_OK; }
     HIPCHK(hipSetDevice(c->device));
     ImageState& I = c->image;
     const size_t nf = target_floats(d, op);
@@ -641,7 +641,7 @@ int bling_image_add_samples(bling_ctx* c, const bling_image_desc* d, int op, con
     add_samples(c, d, op, I.xy.p, I.spectra.p, n, I.target.p, st);
     HIPCHK(hipMemcpyAsync(target, I.target.p, nf * sizeof(float), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    return (int)BLING_OK;
+    return BLING_OK;
   });
 }
 
@@ -653,7 +653,7 @@ int bling_image_add_windowed_device(bling_ctx* c, const bling_image_desc* d, int
     const std::vector<int4> cover = check_windows(d, windows, first, n_windows, n);
     add_windowed(c, d, op, cover, first, static_cast<const float*>(xy), static_cast<const float*>(spectra), n, static_cast<float*>(film),
                  static_cast<float*>(splat), st);
-    return (int)BLING_OK;
+    return BLING_OK;
   });
 }
 
@@ -680,7 +680,7 @@ int bling_image_add_windowed(bling_ctx* c, const bling_image_desc* d, int op, co
     if (film) HIPCHK(hipMemcpyAsync(film, I.target.p, nfilm * sizeof(float), hipMemcpyDeviceToHost, s));
     if (splat) HIPCHK(hipMemcpyAsync(splat, I.target2.p, nsplat * sizeof(float), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    return (int)BLING_OK;
+    return BLING_OK;
   });
 }
 
@@ -695,7 +695,7 @@ int bling_image_scale_splats_device(bling_ctx* c, const bling_image_desc* d, voi
     k_img_scale_splats<<<grid_for((uint32_t)px), 256, 0, c->stream>>>(static_cast<float*>(splat), static_cast<const float*>(factors), scalar, px);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
-    return (int)BLING_OK;
+    return BLING_OK;
   });
 }
 
@@ -712,7 +712,7 @@ int bling_image_develop_device(bling_ctx* c, const bling_image_desc* d, const bl
     HIPCHK(hipSetDevice(c->device));
     develop_launch(c, dp, d->width, d->height, static_cast<const float*>(film), static_cast<const float*>(splat), out);
     HIPCHK(hipStreamSynchronize(c->stream));
-    return (int)BLING_OK;
+    return BLING_OK;
   });
 }
 

@@ -20,17 +20,14 @@ bool li_overlap(const void* a, size_t na, const void* b, size_t nb) {
   return pa < pb + nb && pb < pa + na;
 }
 
-// everything the two entry points refuse, in the order include/bling.h lists it; BLING_OK: go on
-int li_ready(bling_ctx* c) {
+// everything the two entry points refuse, in the order include/bling.h lists it
+void li_ready(bling_ctx* c) {
   if (!c) throw std::invalid_argument("null argument");
-  if (!c->has_scene) { set_last_error("no scene uploaded"); return BLING_ENOSCENE; }
+  need_scene(c);
   if (c->cfg.renderer != BLING_RENDERER_SAMPLER_PATH)
     throw std::invalid_argument("surface_li: the uploaded scene's renderer is not the sampler renderer");
-  if (c->S.integrator == BLING_INTEGRATOR_BIDIR) {
-    set_last_error("surface_li: the bidirectional integrator makes its camera ray inside its walk");
-    return BLING_EUNSUPPORTED;
-  }
-  return BLING_OK;
+  if (c->S.integrator == BLING_INTEGRATOR_BIDIR)
+    throw Refusal(BLING_EUNSUPPORTED, "surface_li: the bidirectional integrator makes its camera ray inside its walk");
 }
 
 int li_wave(bling_ctx* c, const WaveState& W, uint32_t n, uint32_t seed, uint32_t pass) {
@@ -102,7 +99,7 @@ extern "C" {
 int bling_surface_li_device(bling_ctx* c, uint32_t seed, uint32_t pass_index, const void* rays_soa_dev, const void* ids_dev,
                             size_t n, void* L_dev, bling_li_stats* st) {
   return guarded([&] {
-    if (int rc = li_ready(c)) return rc;
+    li_ready(c);
     li_zero_stats(st);
     if (n == 0) return BLING_OK;
     if (!rays_soa_dev || !ids_dev || !L_dev) throw std::invalid_argument("null argument");
@@ -120,7 +117,7 @@ int bling_surface_li_device(bling_ctx* c, uint32_t seed, uint32_t pass_index, co
 int bling_surface_li(bling_ctx* c, uint32_t seed, uint32_t pass_index, const float* rays_soa, const uint32_t* ids, size_t n,
                      float* L_out, bling_li_stats* st) {
   return guarded([&] {
-    if (int rc = li_ready(c)) return rc;
+    li_ready(c);
     li_zero_stats(st);
     if (n == 0) return BLING_OK;
     if (!rays_soa || !ids || !L_out) throw std::invalid_argument("null argument");

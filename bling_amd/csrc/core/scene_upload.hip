@@ -218,7 +218,7 @@ int bling_debug_scene_info(bling_ctx* c, char* buf, size_t size, size_t* len) {
 int bling_debug_bvh(bling_ctx* c, float* nodes, size_t cap_nodes, uint32_t* refs, size_t cap_refs, size_t* n_nodes, size_t* n_refs) {
   return guarded([&] {
     if (!c || !n_nodes || !n_refs) throw std::invalid_argument("null argument");
-    if (!c->has_scene) { set_last_error("no scene uploaded"); return BLING_ENOSCENE; }
+    need_scene(c);
     *n_nodes = c->nodes.n / 4;
     *n_refs = c->refs.n;
     if (!nodes && !refs) return BLING_OK;

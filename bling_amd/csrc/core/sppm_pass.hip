@@ -1,5 +1,6 @@
 // sppm_pass.hip -- host driver of one SPPM pass (Renderer/SPPM.hs onePass) over the kernels of sppm.h.
 #include "core_internal.h"
+#include "ordered_ranges.h"
 
 namespace bcore {
 
@@ -184,38 +185,32 @@ void sppm_pass_t(bling_ctx* c, uint32_t seed, uint32_t pass, float* film, float*
                                                                                             SppmRec{});
     HIPCHK(hipGetLastError());
   } else {
-    // Sampler k's image from zero: its ascending photon ranges, each merged (splat_merge.h) before the next,
-    // then splat = splat + image_k.  A range whose records exceed the buffer is run again with a buffer that
-    // holds them or, beyond the budget, as two halves; its counts, counters and records live in the launch's
-    // own buffers and are taken over only once it fits, so nothing of a redone range counts twice.
+    // Sampler k's image from zero: its photons over the ascending ranges of ordered_ranges.h, each merged
+    // (splat_merge.h) before the next, then splat = splat + image_k.  A launch's counts, counters and records
+    // live in its own buffers and are taken over only once the range fits, so nothing of a redone range counts
+    // twice; the record capacity is carried from sampler to sampler.
     const uint32_t spp = sn * sn;
     const size_t budget = std::min<size_t>(splat_budget(c), 0x7FFFFFFFull);
-    uint32_t cap = splat ? (uint32_t)std::min<size_t>(budget, std::max<size_t>(P.rec.n / 2, (size_t)4 * spp + 1024)) : 0u;
+    uint32_t cap = splat ? ordered_ranges::initial_cap(budget, P.rec.n / 2, spp) : 0u;
     if (splat && P.thread_img.n != 3 * npix) P.thread_img.alloc(3 * npix);
     for (uint32_t k = 0; k < P.nth; ++k) {
       if (splat) HIPCHK(hipMemsetAsync(P.thread_img.p, 0, 3 * npix * sizeof(float), s));
-      uint32_t first = 0, len = spp;
-      while (first < spp) {
-        const uint32_t count = std::min(len, spp - first);
-        unsigned long long ctr[4];
-        launches.emplace_back();
-        const uint32_t got = sppm_launch_rec<F>(c, seed, pass, sn, k, first, count, cap, ctr, launches.back());
-        if (got > cap) {
-          if ((size_t)got <= budget) { cap = got; continue; }            // the same range, into a buffer that holds it
-          if (count == 1)
-            throw std::invalid_argument("sppm: photon " + std::to_string(first) + " of sampler " + std::to_string(k) + " alone writes " +
-                                        std::to_string(got) + " splat records, more than the record budget " + std::to_string(budget));
-          len = (count + 1) / 2;
-          continue;
-        }
-        merges.emplace_back();
-        merges.back().a.record(s);
-        k_sppm_add_u32<<<(P.n_stats + 255) / 256, 256, 0, s>>>(P.cnt.p + (size_t)k * P.n_stats, P.cnt_tmp.p, P.n_stats);
-        if (splat) splat_merge(c, P.rec.p, got, SM_LAYOUT_SPLAT, P.thread_img.p);
-        merges.back().b.record(s);
-        for (int q = 1; q < 4; ++q) sum[q] += ctr[q];
-        first += count;
-      }
+      unsigned long long ctr[4];
+      ordered_ranges::run(
+          spp, budget, cap,
+          [&](uint32_t first, uint32_t count, uint32_t rec_cap) {
+            launches.emplace_back();
+            return sppm_launch_rec<F>(c, seed, pass, sn, k, first, count, rec_cap, ctr, launches.back());
+          },
+          [&](uint32_t, uint32_t, uint32_t got) {
+            merges.emplace_back();
+            merges.back().a.record(s);
+            k_sppm_add_u32<<<(P.n_stats + 255) / 256, 256, 0, s>>>(P.cnt.p + (size_t)k * P.n_stats, P.cnt_tmp.p, P.n_stats);
+            if (splat) splat_merge(c, P.rec.p, got, SM_LAYOUT_SPLAT, P.thread_img.p);
+            merges.back().b.record(s);
+            for (int q = 1; q < 4; ++q) sum[q] += ctr[q];
+          },
+          [&](uint32_t photon) { return "sppm: photon " + std::to_string(photon) + " of sampler " + std::to_string(k); });
       if (splat) {
         merges.emplace_back();
         merges.back().a.record(s);
