@@ -41,7 +41,7 @@ CORE_HDR := $(wildcard bling_amd/csrc/core/*.h) bling_amd/csrc/common/sky_model.
             bling_amd/csrc/common/scene_features.h bling_amd/csrc/common/perlin.h bling_amd/csrc/common/cr_math.h \
             bling_amd/csrc/common/fast_cr.h bling_amd/csrc/common/cellnoise.h bling_amd/csrc/common/image_tex.h \
             bling_amd/csrc/common/gamma_table.h bling_amd/csrc/common/image_sample.h bling_amd/csrc/common/cam_windows.h \
-            bling_amd/csrc/common/lbvh.h
+            bling_amd/csrc/common/lbvh.h bling_amd/csrc/common/bvh4.h
 REF_HDR  := $(wildcard tests/ref/*.h)
 ORA_SRC  := $(wildcard oracle/*.cpp)
 ORA_HDR  := $(wildcard oracle/*.h) include/bling_scene.h bling_amd/csrc/common/perlin.h bling_amd/csrc/common/cr_math.h \

@@ -39,6 +39,38 @@ def host_lbvh(boxes, refs, depth_cap=0, with_keys=False):
     return out + (keys,) if with_keys else out
 
 
+def host_bvh4(nodes):
+    """bling_host_bvh4 (include/bling.h): the host's collapse of a BVH2 ((n, 16) float32, as Context.bvh() and
+    host_lbvh return it) into the BVH4, no context and no GPU.  Returns (nodes4 (m, 28) float32, {"depth",
+    "stack_need"}).  render.BlingError for a BVH2 whose links form no tree."""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _ffi
+    from .render import _check
+    n2 = np.ascontiguousarray(nodes, np.float32).reshape(-1, 16)
+    out = np.zeros((len(n2), 28), np.float32)
+    n4, depth, need = C.c_size_t(), C.c_int(), C.c_int()
+    _check(_ffi.hip().bling_host_bvh4(_ffi.f32ptr(n2), len(n2), _ffi.f32ptr(out), len(out), C.byref(n4), C.byref(depth), C.byref(need)))
+    return out[:int(n4.value)].copy(), {"depth": int(depth.value), "stack_need": int(need.value)}
+
+
+def host_threaded(nodes):
+    """bling_host_threaded (include/bling.h): the host's threaded entry list of a BVH2, (e, 8) float32."""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _ffi
+    from .render import _check
+    n2 = np.ascontiguousarray(nodes, np.float32).reshape(-1, 16)
+    out = np.zeros((2 * len(n2), 8), np.float32)
+    ne = C.c_size_t()
+    _check(_ffi.hip().bling_host_threaded(_ffi.f32ptr(n2), len(n2), _ffi.f32ptr(out), len(out), C.byref(ne)))
+    return out[:int(ne.value)].copy()
+
+
 def scene_plan(job) -> dict:
     """bling_debug_scene_plan (include/bling.h): the acceleration / kernel plan an upload of the job would settle
     with the host builder -- Context.scene_info()'s dict -- from the description alone, no context and no GPU.

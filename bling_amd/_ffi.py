@@ -178,6 +178,17 @@ BVH_BUILDERS = {"host": 0, "device": 1}                                         
 BVH_FALLBACKS = ["none", "fractal", "items", "depth", "refs"]                    # BLING_BVH_FALLBACK_*
 
 
+DERIVE_PATHS = {"host": 0, "device": 1}                                          # BLING_DERIVE_*; the device bit of flags
+DERIVE_FALLBACKS = ["none", "fractal", "devices", "nodes"]                       # BLING_DERIVE_FALLBACK_*
+
+
+class DeriveInfo(C.Structure):
+    """bling_derive_info (include/bling.h)."""
+    _fields_ = [("requested", C.c_uint32), ("used", C.c_uint32), ("fallback", C.c_uint32), ("bvh4_nodes", C.c_uint32),
+                ("bvh4_depth", C.c_uint32), ("stack_need", C.c_uint32), ("level_launches", C.c_uint32), ("reserved", C.c_uint32),
+                ("ms_derive_device", C.c_double), ("ms_plan_host", C.c_double)]
+
+
 class UploadParams(C.Structure):
     """bling_upload_params (include/bling.h)."""
     _fields_ = [("bvh_builder", C.c_uint32), ("flags", C.c_uint32)]
@@ -283,7 +294,7 @@ HIP_SYMBOLS = ["bling_create", "bling_scene_upload", "bling_scene_validate", "bl
                "bling_surface_li_device", "bling_surface_li", "bling_debug_set_li_chunk",
                "bling_camera_samples_device", "bling_camera_samples",
                "bling_scene_upload_with", "bling_debug_bvh", "bling_debug_bvh_build_info", "bling_debug_set_bvh_depth_cap",
-               "bling_debug_scene_plan",
+               "bling_debug_scene_plan", "bling_debug_derived", "bling_debug_derive_info", "bling_host_bvh4", "bling_host_threaded",
                "bling_destroy", "bling_last_error", "bling_version"]
 
 
@@ -462,6 +473,16 @@ def hip() -> C.CDLL:
             lib.bling_debug_bvh_build_info.restype = C.c_int
             lib.bling_debug_set_bvh_depth_cap.argtypes = [C.c_void_p, C.c_int]
             lib.bling_debug_set_bvh_depth_cap.restype = C.c_int
+        if hasattr(lib, "bling_debug_derived"):       # older experiment builds lack the device derivation
+            c_szp = C.POINTER(C.c_size_t)
+            lib.bling_debug_derived.argtypes = [C.c_void_p, c_f32p, C.c_size_t, c_f32p, C.c_size_t, c_f32p, C.c_size_t, c_szp, c_szp, c_szp]
+            lib.bling_debug_derived.restype = C.c_int
+            lib.bling_debug_derive_info.argtypes = [C.c_void_p, C.POINTER(DeriveInfo)]
+            lib.bling_debug_derive_info.restype = C.c_int
+            lib.bling_host_bvh4.argtypes = [c_f32p, C.c_size_t, c_f32p, C.c_size_t, c_szp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+            lib.bling_host_bvh4.restype = C.c_int
+            lib.bling_host_threaded.argtypes = [c_f32p, C.c_size_t, c_f32p, C.c_size_t, c_szp]
+            lib.bling_host_threaded.restype = C.c_int
         lib.bling_destroy.argtypes = [C.c_void_p]
         lib.bling_last_error.restype = C.c_char_p
         lib.bling_version.restype = C.c_char_p

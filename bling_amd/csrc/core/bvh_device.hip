@@ -1,7 +1,8 @@
 // bvh_device.hip -- the scene BVH built on the device: the linear BVH of common/lbvh.h (Morton keys,
 // radix sort, common-prefix hierarchy, bottom-up bounds, leaves of one or two items) in the node and
 // leaf format of the host's SAH tree (bvh_build.h), read back once so that everything derived from a
-// bvh::Result runs unchanged on it.  The host restatement is bling_host_lbvh (host/lbvh_host.cpp).
+// bvh::Result runs unchanged on it -- or left in the context's buffers for bvh_derive.hip.  The host
+// restatement is bling_host_lbvh (host/lbvh_host.cpp).
 //
 //   k_lbvh_centres / k_lbvh_centres_final   bounds of the box centres (two-stage min / max) and the axis scales
 //   k_lbvh_keys                             key = Morton code << 32 | item index
@@ -318,7 +319,7 @@ inline uint32_t blocks_for(size_t n, size_t per) { return (uint32_t)((n + per - 
 namespace bcore {
 
 bool lbvh_build_device(bling_ctx* c, const std::vector<bvh::Box>& boxes, const std::vector<uint32_t>& refs, int depth_cap,
-                       bvh::Result& R, float* ms, int* depth) {
+                       bvh::Result& R, float* ms, int* depth, uint32_t* n_kept) {
   static_assert(sizeof(bvh::Box) == 6 * sizeof(float), "a Box is lo.xyz, hi.xyz");
   const size_t n_items = boxes.size();
   if (n_items < 3 || n_items > blbvh::kMaxItems || refs.size() != n_items) throw std::invalid_argument("lbvh: item count out of range");
@@ -388,11 +389,20 @@ bool lbvh_build_device(bling_ctx* c, const std::vector<bvh::Box>& boxes, const s
   if (stats[0] < 1 || stats[0] > n - 1) throw std::runtime_error("lbvh: node count out of range");
   if ((int)stats[1] > depth_cap) return false;
   bvh::Result out;
+  out.depth = (int)stats[1]; out.leaves = (int)stats[2]; out.max_leaf = (int)stats[3];
+  if (n_kept) {                                            // the tree stays: the nodes at their size, the refs as they are
+    c->nodes.alloc((size_t)4 * stats[0]);
+    HIPCHK(hipMemcpy(c->nodes.p, d_nodes.p, (size_t)4 * stats[0] * sizeof(float4), hipMemcpyDeviceToDevice));
+    std::swap(c->refs.p, d_refs_out.p);
+    std::swap(c->refs.n, d_refs_out.n);
+    *n_kept = stats[0];
+    R = std::move(out);
+    return true;
+  }
   out.nodes.resize((size_t)16 * stats[0]);
   out.refs.resize(n);
   HIPCHK(hipMemcpy(out.nodes.data(), d_nodes.p, out.nodes.size() * sizeof(float), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(out.refs.data(), d_refs_out.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  out.depth = (int)stats[1]; out.leaves = (int)stats[2]; out.max_leaf = (int)stats[3];
   R = std::move(out);
   return true;
 }

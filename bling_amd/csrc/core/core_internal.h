@@ -266,9 +266,14 @@ void develop_launch(bling_ctx* c, const bling_develop_params* dp, const float* f
 void develop_launch(bling_ctx* c, const bling_develop_params* dp, int w, int h, const float* film, const float* splat, void* out);
 // bvh_device.hip: the linear BVH of common/lbvh.h over the items (3 <= n <= 2^24), built on the context's device
 // and read back into R once.  false, with R untouched, when the tree is deeper than depth_cap (*depth holds
-// its depth).  *ms: HIP events around the kernels.
+// its depth).  *ms: HIP events around the kernels.  With n_kept, the tree stays on the device instead: the nodes go
+// to c->nodes and the refs to c->refs, *n_kept receives the node count, and R holds depth, leaves and max_leaf alone.
 bool lbvh_build_device(bling_ctx* c, const std::vector<bvh::Box>& boxes, const std::vector<uint32_t>& refs, int depth_cap,
-                       bvh::Result& R, float* ms, int* depth);
+                       bvh::Result& R, float* ms, int* depth, uint32_t* n_kept = nullptr);
+// bvh_derive.hip: the leaf records (c->leaf_geo) and the BVH4 (c->nodes4) of the BVH2 in c->nodes / c->refs over the
+// n_tris triangle records of c->tri_geo, on the context's device (common/bvh4.h).  k.n2 and k.nrefs go in; k.n4,
+// k.bvh4_depth and k.stack_need come out, and info's bvh4_*, stack_need, level_launches and ms_derive_device.
+void bvh_derive_device(bling_ctx* c, uint32_t n_tris, bplan::DeriveCounts& k, bling_derive_info* info);
 }  // namespace bcore
 
 // the context lives in the global namespace (include/bling.h declares `struct bling_ctx`)
@@ -371,6 +376,7 @@ struct bling_ctx {
   bplan::PlanSummary plan_info;      // bling_debug_scene_info
   bling_bvh_build_info bvh_info{};   // how the uploaded BVH2 was built (bling_debug_bvh_build_info)
   int bvh_depth_cap = 0;             // bling_debug_set_bvh_depth_cap: 0 = STACK_DEPTH - 1
+  bling_derive_info derive_info{};   // where what follows the BVH2 was derived (bling_debug_derive_info)
   uint32_t features = FT_ALL;   // scene_features() of the uploaded scene
   size_t lds_trace = 0;         // dynamic LDS bytes of the traversal kernels
   bool lds_all = false;         // the whole BVH, triangle set and leaf refs are LDS-resident

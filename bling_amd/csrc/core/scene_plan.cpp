@@ -345,15 +345,45 @@ SceneItems scene_items(const bling_scene_desc& d) {
 bvh::Result host_bvh2(const SceneItems& items) { return bvh::build(items.boxes, items.refs, 2); }
 
 ScenePlan scene_derive(const bling_scene_desc& d, SceneItems&& items, bvh::Result&& bvh2) {
+  const bvh::Result& R = bvh2;
+  const uint32_t nrefs = (uint32_t)R.refs.size();
+  // the primitives' records in leaf order, the ref in each, one zero record behind them (the layout:
+  // dev_trace.h LeafRec, common/bvh4.h leaf_quad).  The BVH4 kernels with a global fallback test a leaf primitive
+  // with one dependent load instead of two; the all-LDS kernels copy the records into LDS as they are.
+  std::vector<float4> lg(leaf_geo_quads(nrefs), make_float4(0.f, 0.f, 0.f, 0.f));
+  for (size_t j = 0; j < nrefs; ++j) {
+    const uint32_t ref = R.refs[j], idx = ref & 0x3FFFFFFFu;
+    if ((ref >> 30) == REF_TRI) { lg[3 * j] = items.geo[3 * idx]; lg[3 * j + 1] = items.geo[3 * idx + 1]; }
+    float rf;
+    std::memcpy(&rf, &ref, sizeof rf);
+    lg[3 * j + 2] = make_float4((ref >> 30) == REF_TRI ? items.geo[3 * idx + 2].x : 0.f, rf, 0.f, 0.f);
+  }
+  if (lg.size() != (size_t)3 * (nrefs + 1)) throw std::runtime_error("leaf_geo: not 3 x (refs + 1) records");
+  if (R.depth > STACK_DEPTH - 1) throw std::runtime_error("BVH deeper than the traversal stack");
+  // the 4-wide tree for the queue traversal kernels of non-fractal profiles (Traversal4), and the threaded list
+  // of the wave-coherent walk (packet_walk, dev_trace.h)
+  bvh::Result4 Q = bvh::collapse4(R);
+  std::vector<float> pkt = bvh::threaded(R);
+  DeriveCounts k;
+  k.n2 = (uint32_t)(R.nodes.size() / 16); k.nrefs = nrefs;
+  k.bvh_depth = R.depth; k.bvh_leaves = R.leaves; k.max_leaf = R.max_leaf;
+  k.n4 = (uint32_t)(Q.nodes.size() / 28); k.bvh4_depth = Q.depth; k.stack_need = Q.stack_need;
+  k.pkt_entries = (uint32_t)(pkt.size() / 8);
+  ScenePlan P = scene_plan_counts(d, std::move(items), k);
+  P.bvh2 = std::move(bvh2);
+  P.leaf_geo = std::move(lg);
+  P.nodes4 = std::move(Q.nodes);
+  P.pkt = std::move(pkt);
+  return P;
+}
+
+ScenePlan scene_plan_counts(const bling_scene_desc& d, SceneItems&& items, const DeriveCounts& k) {
   ScenePlan P;
   P.items = std::move(items);
-  P.bvh2 = std::move(bvh2);
   const SceneItems& I = P.items;
   std::vector<bvh::Box>().swap(P.items.boxes);   // the tree is built: its items are not kept for the uploads
   std::vector<uint32_t>().swap(P.items.refs);
-  const bvh::Result& R = P.bvh2;
-  const uint32_t nt = d.num_triangles, ns = d.num_shapes, nrefs = (uint32_t)R.refs.size();
-  const uint32_t n2 = (uint32_t)(R.nodes.size() / 16);
+  const uint32_t nt = d.num_triangles, ns = d.num_shapes, nrefs = k.nrefs, n2 = k.n2;
   const bool fractal = I.fractal_prim >= 0;
   DevScene& S = P.S;
   PlanSummary& info = P.info;
@@ -361,50 +391,31 @@ ScenePlan scene_derive(const bling_scene_desc& d, SceneItems&& items, bvh::Resul
   S.world_r = I.world_r;
   std::memcpy(S.kd_lo, I.kd_lo, sizeof S.kd_lo);
   std::memcpy(S.kd_hi, I.kd_hi, sizeof S.kd_hi);
-  {
-    // the primitives' records in leaf order, the ref in each, one zero record behind them (the layout:
-    // dev_trace.h LeafRec).  The BVH4 kernels with a global fallback test a leaf primitive with one
-    // dependent load instead of two; the all-LDS kernels copy the records into LDS as they are.
-    std::vector<float4>& lg = P.leaf_geo;
-    lg.assign(leaf_geo_quads(nrefs), make_float4(0.f, 0.f, 0.f, 0.f));
-    for (size_t j = 0; j < nrefs; ++j) {
-      const uint32_t ref = R.refs[j], idx = ref & 0x3FFFFFFFu;
-      if ((ref >> 30) == REF_TRI) { lg[3 * j] = I.geo[3 * idx]; lg[3 * j + 1] = I.geo[3 * idx + 1]; }
-      float rf;
-      std::memcpy(&rf, &ref, sizeof rf);
-      lg[3 * j + 2] = make_float4((ref >> 30) == REF_TRI ? I.geo[3 * idx + 2].x : 0.f, rf, 0.f, 0.f);
-    }
-    if (lg.size() != (size_t)3 * (nrefs + 1)) throw std::runtime_error("leaf_geo: not 3 x (refs + 1) records");
-  }
   info.prims = d.num_prims;
-  info.bvh_depth = R.depth; info.bvh_leaves = R.leaves; info.max_leaf = R.max_leaf;
-  if (R.depth > STACK_DEPTH - 1) throw std::runtime_error("BVH deeper than the traversal stack");
+  info.bvh_depth = k.bvh_depth; info.bvh_leaves = k.bvh_leaves; info.max_leaf = k.max_leaf;
+  if (k.bvh_depth > STACK_DEPTH - 1) throw std::runtime_error("BVH deeper than the traversal stack");
   info.features = bfeat::scene_features(&d);
   static_assert(FT_PROCTEX == bfeat::PROCTEX && FT_BUMP == bfeat::BUMP && FT_MATTE == bfeat::MATTE &&
                 FT_MULTI_LIGHT == bfeat::MULTI_LIGHT, "feature bits");
   S.num_nodes = n2;
-  plan_lds(S, n2, nt, nrefs, (uint32_t)R.depth + 1);
+  plan_lds(S, n2, nt, nrefs, (uint32_t)k.bvh_depth + 1);
   P.lds_trace = lds_bytes(S.lds_nodes, S.lds_tris, S.lds_refs, S.stack_depth);
   P.lds_all = S.lds_nodes == n2 && S.lds_tris == nt && S.lds_refs == nrefs;
   {
-    // the 4-wide tree for the queue traversal kernels of non-fractal profiles (Traversal4)
-    bvh::Result4 Q = bvh::collapse4(R);
-    const uint32_t n4 = (uint32_t)(Q.nodes.size() / 28);
-    plan_lds4(S, n4, nt, nrefs, (uint32_t)std::max(1, Q.stack_need), ns);
+    const uint32_t n4 = k.n4;
+    plan_lds4(S, n4, nt, nrefs, (uint32_t)std::max(1, k.stack_need), ns);
     info.lds_all4 = S.lds4_nodes == n4 && S.lds4_tris == nt && S.lds4_refs == nrefs &&
                     S.stack4_lds == S.stack4_need && S.lds4_shapes == ns;
     // the all-LDS kernels lay the primitives out in leaf order (dev_trace.h lds_setup<..., LEAF>)
     info.lds_trace4 = info.lds_all4 ? lds_bytes4_leaf(S.lds4_nodes, S.lds4_refs, S.stack4_lds, S.lds4_shapes)
                                     : lds_bytes4(S.lds4_nodes, S.lds4_tris, S.lds4_refs, S.stack4_lds, S.lds4_shapes);
-    info.bvh4_depth = Q.depth;
+    info.bvh4_depth = k.bvh4_depth;
     S.num_nodes4 = n4;
-    P.nodes4 = std::move(Q.nodes);
   }
   {
     // small scenes walk the threaded BVH wave-coherently (packet_walk, dev_trace.h): at most
     // kPacketMaxEntries child boxes, no fractal
-    P.pkt = bvh::threaded(R);
-    const uint32_t ne = (uint32_t)(P.pkt.size() / 8);
+    const uint32_t ne = k.pkt_entries;
     const bool on = !fractal && ne > 0 && ne <= kPacketMaxEntries;
     S.pkt_n = on ? ne : 0u;
     S.pkt_refs = nrefs;

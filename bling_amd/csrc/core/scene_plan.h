@@ -3,7 +3,7 @@
 //   scene_items      triangle records, the primitives' boxes and refs in reference order, world bounds
 //   scene_derive     everything after the BVH2 (built by either builder, scene_upload.hip): leaf records, BVH4,
 //                    threaded list, the LDS plans and kernel switches, shape records, light tables and the
-//                    scalar half of DevScene
+//                    scalar half of DevScene; scene_plan_counts is its second half, which the sizes alone decide
 // scene_plan.cpp makes no HIP runtime call: bling_debug_scene_plan answers on a machine without a GPU, and a
 // multi-device upload derives once and copies the one plan to every device.
 #pragma once
@@ -57,10 +57,23 @@ struct ScenePlan {
   PlanSummary info;                   // with scene_features() of the description and the BVH4 plan's LDS bytes
 };
 
+// The sizes of the two trees and the threaded list: all the plan needs of them.
+struct DeriveCounts {
+  uint32_t n2 = 0, nrefs = 0;                       // BVH2 nodes, leaf refs
+  int bvh_depth = 0, bvh_leaves = 0, max_leaf = 0;  // bvh::Result
+  uint32_t n4 = 0;                                  // BVH4 nodes ...
+  int bvh4_depth = 0, stack_need = 0;               // ... and bvh::Result4
+  uint32_t pkt_entries = 0;                         // entries of the threaded list (0: none was derived)
+};
+
 void validate_scene(const bling_scene_desc* d);
 SceneItems scene_items(const bling_scene_desc& d);
 // consumes the items and the tree: their arrays move into the plan
 ScenePlan scene_derive(const bling_scene_desc& d, SceneItems&& items, bvh::Result&& bvh2);
+// the part of scene_derive that needs the counts alone: the LDS plans, the packet and brute switches, shape records,
+// light tables, the scalar half of DevScene and the summary.  scene_derive ends in it; an upload that derives the
+// arrays on the device (bvh_derive.hip) calls it with the counts read back.  bvh2, leaf_geo, nodes4 and pkt stay empty.
+ScenePlan scene_plan_counts(const bling_scene_desc& d, SceneItems&& items, const DeriveCounts& k);
 // the BVH2 of the items by the host's binned SAH, as every upload that does not use the device builder builds it
 bvh::Result host_bvh2(const SceneItems& items);
 // the summary as the JSON object of bling_debug_scene_info and bling_debug_scene_plan

@@ -3,7 +3,7 @@
 // pass-NNNNN.png and .hdr at PassDone) over the host loader and the MI355X core.
 //
 //   bling <scene.bling> [--overrides "image=W,H;..."] [--passes N] [--out prefix] [--device D]
-//         [--develop host|device] [--splat atomic|ordered] [--film atomic|ordered] [--bvh host|device]
+//         [--develop host|device] [--splat atomic|ordered] [--film atomic|ordered] [--bvh host|device] [--derive host|device]
 // --develop device makes each written pass's 8-bit and RGBE pixels on the device (bling_film_develop)
 // and hands them to the encoders; the default, host, develops with the host library.  Same files.
 // --splat ordered (light tracer, Metropolis and SPPM scenes) adds every pixel's splats in the reference's order
@@ -301,7 +301,7 @@ int image_filters(int argc, char** argv) {
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    std::fprintf(stderr, "usage: %s scene.bling [--overrides S] [--passes N] [--out prefix] [--device D] [--develop host|device] [--splat atomic|ordered] [--film atomic|ordered] [--seams] [--bvh host|device]\n"
+    std::fprintf(stderr, "usage: %s scene.bling [--overrides S] [--passes N] [--out prefix] [--device D] [--develop host|device] [--splat atomic|ordered] [--film atomic|ordered] [--seams] [--bvh host|device] [--derive host|device]\n"
                          "       %s --image-filters [--out DIR] [--size WxH] [--develop host|device] [--device D] [--windows N]\n", argv[0], argv[0]);
     return 2;
   }
@@ -316,6 +316,8 @@ int main(int argc, char** argv) {
   bool seams = false;
   uint32_t bvh_builder = BLING_BVH_HOST;
   bool bvh_line = false;
+  uint32_t upload_flags = 0u;
+  bool derive_line = false;
   for (int i = 2; i < argc; i += 2) {
     if (!std::strcmp(argv[i], "--seams")) { seams = true; --i; continue; }   // the one switch without a value
     if (i + 1 >= argc) break;
@@ -348,6 +350,13 @@ int main(int argc, char** argv) {
       }
       bvh_builder = !std::strcmp(argv[i + 1], "device") ? BLING_BVH_DEVICE : BLING_BVH_HOST;
       bvh_line = true;
+    } else if (!std::strcmp(argv[i], "--derive")) {
+      if (std::strcmp(argv[i + 1], "host") && std::strcmp(argv[i + 1], "device")) {
+        std::fprintf(stderr, "--derive takes host or device, not %s\n", argv[i + 1]);
+        return 2;
+      }
+      upload_flags = !std::strcmp(argv[i + 1], "device") ? BLING_UPLOAD_DERIVE_DEVICE : 0u;
+      derive_line = true;
     }
   }
   bling_host_scene* hs = nullptr;
@@ -355,7 +364,7 @@ int main(int argc, char** argv) {
   std::printf("Job Stats\n   %s\n", bling_host_summary(hs));
   const bling_scene_desc* d = bling_host_desc(hs);
   bling_ctx* ctx = nullptr;
-  const bling_upload_params up{bvh_builder, 0u};
+  const bling_upload_params up{bvh_builder, upload_flags};
   if (bling_create(&device, 1, &ctx) != 0 || bling_scene_upload_with(ctx, d, &up) != 0) {
     std::fprintf(stderr, "%s\n", bling_last_error());
     return 1;
@@ -368,6 +377,15 @@ int main(int argc, char** argv) {
     std::printf("bvh: builder %s%s, %u items, %u nodes, depth %u, build %.3f ms, derive %.3f ms\n",
                 bi.used == BLING_BVH_DEVICE ? "device" : "host", why[bi.fallback <= 4 ? bi.fallback : 0], bi.items, bi.nodes,
                 bi.depth, bi.ms_build, bi.ms_derive);
+  }
+  if (derive_line) {                   // --derive: where the BVH4, the leaf records and the plans were derived
+    bling_derive_info di;
+    if (bling_debug_derive_info(ctx, &di) != 0) { std::fprintf(stderr, "%s\n", bling_last_error()); return 1; }
+    static const char* const why[] = {"", " (fractal scene: host derivation)", " (several devices: host derivation)",
+                                      " (no BVH2 nodes: host derivation)"};
+    std::printf("derive: %s%s, %u BVH4 nodes, depth %u, stack %u, %u levels, device %.3f ms, host %.3f ms\n",
+                di.used == BLING_DERIVE_DEVICE ? "device" : "host", why[di.fallback <= 3 ? di.fallback : 0], di.bvh4_nodes,
+                di.bvh4_depth, di.stack_need, di.level_launches, di.ms_derive_device, di.ms_plan_host);
   }
   int w = d->config.width, h = d->config.height;
   std::vector<float> film((size_t)w * h * 4, 0.f), rgb((size_t)w * h * 3);

@@ -123,18 +123,48 @@ class Context:
         self.devices = ids
         self.job: Job | None = None
 
-    def upload(self, job: Job, bvh: str | int | None = None):
+    def upload(self, job: Job, bvh: str | int | None = None, derive: str | None = None):
         """bling_scene_upload (replaces Scene.mkScene -> mkKdTree).  bvh: "host" (the default: the binned SAH
         on the host) or "device" (the linear BVH built on the device, bling_scene_upload_with); an integer is
-        passed on as the BLING_BVH_* value it is."""
-        if bvh is None:
+        passed on as the BLING_BVH_* value it is.  derive: "host" (the default) or "device": the BVH4 and the leaf
+        records derived from the BVH2 on the device (BLING_UPLOAD_DERIVE_DEVICE)."""
+        if bvh is None and derive is None:
             _check(_ffi.hip().bling_scene_upload(self._h, C.c_void_p(job.desc)))
         else:
             if isinstance(bvh, str) and bvh not in _ffi.BVH_BUILDERS:
                 raise ValueError(f"bvh is 'host' or 'device', not {bvh!r}")
-            up = _ffi.UploadParams(_ffi.BVH_BUILDERS[bvh] if isinstance(bvh, str) else int(bvh), 0)
+            if derive is not None and derive not in _ffi.DERIVE_PATHS:
+                raise ValueError(f"derive is 'host' or 'device', not {derive!r}")
+            flags = _ffi.DERIVE_PATHS[derive] if derive is not None else 0
+            builder = 0 if bvh is None else _ffi.BVH_BUILDERS[bvh] if isinstance(bvh, str) else int(bvh)
+            up = _ffi.UploadParams(builder, flags)
             _check(_ffi.hip().bling_scene_upload_with(self._h, C.c_void_p(job.desc), C.byref(up)))
         self.job = job
+
+    def derived(self) -> dict:
+        """bling_debug_derived: what the kernels walk besides the BVH2, read back from the device, whichever path
+        derived it: {"nodes4": (n, 28) float32, "leaf_geo": (m, 4) float32, "pkt": (e, 8) float32} (pkt: the
+        entries the packet kernels walk; none when the list is too long).  Links are int32 bit patterns."""
+        n4, nl, ne = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        lib = _ffi.hip()
+        _check(lib.bling_debug_derived(self._h, None, 0, None, 0, None, 0, C.byref(n4), C.byref(nl), C.byref(ne)))
+        out = {"nodes4": np.zeros((int(n4.value), 28), np.float32), "leaf_geo": np.zeros((int(nl.value), 4), np.float32),
+               "pkt": np.zeros((int(ne.value), 8), np.float32)}
+        _check(lib.bling_debug_derived(self._h, _ffi.f32ptr(out["nodes4"]), n4.value, _ffi.f32ptr(out["leaf_geo"]), nl.value,
+                                       _ffi.f32ptr(out["pkt"]), ne.value, C.byref(n4), C.byref(nl), C.byref(ne)))
+        return out
+
+    def derive_info(self) -> dict:
+        """bling_debug_derive_info: where the BVH4, leaf records and plans were derived: requested / used ("host" /
+        "device"), fallback ("none", "fractal", "devices", "nodes"), bvh4_nodes, bvh4_depth, stack_need,
+        level_launches, ms_derive_device, ms_plan_host."""
+        di = _ffi.DeriveInfo()
+        _check(_ffi.hip().bling_debug_derive_info(self._h, C.byref(di)))
+        names = {v: k for k, v in _ffi.DERIVE_PATHS.items()}
+        out = {k: getattr(di, k) for k, _ in di._fields_ if k != "reserved"}
+        out["requested"], out["used"] = names[di.requested], names[di.used]
+        out["fallback"] = _ffi.DERIVE_FALLBACKS[di.fallback]
+        return out
 
     def bvh(self):
         """bling_debug_bvh: the uploaded BVH2 as (nodes (n, 16) float32, refs (m,) uint32), whichever builder

@@ -154,13 +154,24 @@ int bling_scene_upload(bling_ctx* ctx, const bling_scene_desc* desc);
  * context receive the arrays built on the first device.
  * The device builder stands down -- the upload succeeds with the host tree, and bling_debug_bvh_build_info
  * names the reason -- for a fractal scene, for fewer than three items, for a tree deeper than the traversal
- * stack allows (31) and for more than 2^24 items.  flags must be 0.  A bvh_builder other than the two is
- * BLING_EINVAL. */
+ * stack allows (31) and for more than 2^24 items.  A bvh_builder other than the two is BLING_EINVAL.
+ *
+ * flags: 0, or BLING_UPLOAD_DERIVE_DEVICE; any other bit is BLING_EINVAL.  With the bit, what follows the BVH2 is
+ * derived on device_ids[0] (csrc/common/bvh4.h, csrc/core/bvh_derive.hip): the leaf records by a gather, the BVH4
+ * level by level.  Each array is bit for bit the host derivation's of the same BVH2.  A host-built tree is
+ * uploaded once and a device-built one never leaves the device: only counts come back, and the LDS plans are
+ * settled from them on the host.  The threaded list is the one exception: it is walked only when it has at most
+ * 16 entries, so a BVH2 of more than 16 nodes gets none (pkt_n = 0, as on the host path), and a smaller one (at
+ * most 1 KiB) is read back and threaded on the host.
+ * The device derivation stands down -- the upload succeeds with the host derivation, and
+ * bling_debug_derive_info names the reason -- for a fractal scene, for a context of several devices (the peers
+ * receive the host's plan) and for a BVH2 without nodes. */
 #define BLING_BVH_HOST   0u
 #define BLING_BVH_DEVICE 1u
+#define BLING_UPLOAD_DERIVE_DEVICE 1u
 typedef struct bling_upload_params {
   uint32_t bvh_builder;     /* BLING_BVH_* */
-  uint32_t flags;           /* 0 */
+  uint32_t flags;           /* 0 or BLING_UPLOAD_DERIVE_DEVICE */
 } bling_upload_params;
 int bling_scene_upload_with(bling_ctx* ctx, const bling_scene_desc* desc, const bling_upload_params* params);
 
@@ -795,6 +806,17 @@ int bling_debug_scene_info(bling_ctx* ctx, char* buf, size_t size, size_t* len);
  * whose refusals it shares (BLING_EINVAL with the reason). */
 int bling_debug_scene_plan(const bling_scene_desc* desc, char* buf, size_t size, size_t* len);
 
+/* The host's derivation of the BVH4 and of the threaded list from a BVH2 (n2 nodes of 16 floats, as
+ * bling_debug_bvh and bling_host_lbvh return them), without a context or a device: the specification the device
+ * derivation is pinned to (csrc/common/bvh4.h).  A link must name a node of the array, and no node may be named
+ * twice or name the root: BLING_EINVAL otherwise.
+ *   bling_host_bvh4: nodes4_out (may be NULL) has room for cap_nodes4 nodes of 28 floats; *n4 always receives
+ *     the node count (at most n2), *depth and *stack_need the BVH4's depth and stack bound; the nodes are written
+ *     only when cap_nodes4 suffices (BLING_EINVAL otherwise, with nothing written).
+ *   bling_host_threaded: the same for the entry list, 8 words an entry, at most 2 n2 entries. */
+int bling_host_bvh4(const float* nodes2, size_t n2, float* nodes4_out, size_t cap_nodes4, size_t* n4, int* depth, int* stack_need);
+int bling_host_threaded(const float* nodes2, size_t n2, float* entries_out, size_t cap_entries, size_t* n_entries);
+
 /* Diagnostics: the uploaded scene's BVH2 as the kernels walk it, whichever builder made it, read back from
  * device_ids[0]: 16 floats per node (two child boxes, two links, two zero words) and the leaf refs.  *n_nodes
  * and *n_refs always receive the sizes; nodes and refs (either may be NULL) are written only when both
@@ -819,6 +841,33 @@ typedef struct bling_bvh_build_info {
 int bling_debug_bvh_build_info(bling_ctx* ctx, bling_bvh_build_info* out);
 /* Test hook: the depth above which the device builder stands down, 1 .. 31; 0 restores 31. */
 int bling_debug_set_bvh_depth_cap(bling_ctx* ctx, int cap);
+
+/* Diagnostics: what the uploaded scene's kernels walk besides the BVH2, whichever path derived it, read back
+ * from device_ids[0]: the BVH4 (28 floats a node), the leaf records (float4s: three per leaf ref and one zero
+ * record of three behind them) and the threaded list as it is walked (8 words an entry: the scene plan's pkt_n
+ * entries, none when the list is too long to be walked).  *n_nodes4, *n_leaf_quads and *n_pkt always receive
+ * the sizes (nodes, float4s, entries); the arrays (any may be NULL) are written only when every capacity given
+ * with a non-NULL array suffices -- BLING_EINVAL otherwise, with nothing written. */
+int bling_debug_derived(bling_ctx* ctx, float* nodes4, size_t cap_nodes4, float* leaf_geo, size_t cap_leaf_quads, float* pkt,
+                        size_t cap_pkt, size_t* n_nodes4, size_t* n_leaf_quads, size_t* n_pkt);
+
+/* Diagnostics: where the uploaded scene's BVH4, leaf records and plans were derived. */
+#define BLING_DERIVE_HOST   0u
+#define BLING_DERIVE_DEVICE 1u
+#define BLING_DERIVE_FALLBACK_NONE     0u
+#define BLING_DERIVE_FALLBACK_FRACTAL  1u   /* a fractal scene: its profiles walk the BVH2 in the host path's leaf order */
+#define BLING_DERIVE_FALLBACK_DEVICES  2u   /* a context of several devices: the peers receive the host's plan */
+#define BLING_DERIVE_FALLBACK_NODES    3u   /* a BVH2 without nodes */
+typedef struct bling_derive_info {
+  uint32_t requested, used;       /* BLING_DERIVE_* */
+  uint32_t fallback;              /* BLING_DERIVE_FALLBACK_*: why used differs from requested */
+  uint32_t bvh4_nodes, bvh4_depth, stack_need;
+  uint32_t level_launches;        /* device: BVH4 levels, each one open / scan / link round; host: 0 */
+  uint32_t reserved;
+  double ms_derive_device;        /* device: HIP events around the derive kernels (the per-level count read-backs included) */
+  double ms_plan_host;            /* host wall time of the host's share: the whole derivation, or the plan from the counts */
+} bling_derive_info;
+int bling_debug_derive_info(bling_ctx* ctx, bling_derive_info* out);
 
 /* Frees every device resource of the context. */
 void bling_destroy(bling_ctx* ctx);

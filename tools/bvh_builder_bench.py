@@ -2,10 +2,12 @@
 """Build time and tree quality of the two BVH builders (bling_scene_upload_with: the host's binned SAH and
 the device's linear BVH), measured through bling_debug_bvh_build_info.  Reads nothing outside the repository.
 
-  python tools/bvh_builder_bench.py [--name NAME] [--soup N] [--skip-soup]
+  python tools/bvh_builder_bench.py [--name NAME] [--soup N] [--skip-soup] [--derive host,device]
 
-writes profiles/NAME.jsonl: one line per (scene, builder, upload) with ms_build and ms_derive -- one warm-up
-upload, then three -- and one line per builder with node_visits, tri_tests and ms_closest of a pass over ducky
+writes profiles/NAME.jsonl: one line per (scene, builder, derivation, upload) with ms_build, ms_derive (host wall
+time of everything after the BVH2), ms_derive_device (HIP events around the derive kernels), ms_plan_host (the
+host's share) and ms_upload (wall time of the whole upload call) -- one warm-up upload, then three -- and one line
+per builder with node_visits, tri_tests and ms_closest of a pass over ducky
 at 48 x 48 (BLING_PASS_TRAVERSAL_STATS | BLING_PASS_KERNEL_TIMING).  Scenes:
   ducky    fixtures/scenes/ducky.bling (14 129 items)
   bezier   fixtures/scenes/bezier.bling with both patches at subdivs 81: 26 244 triangles, the size of the
@@ -18,6 +20,7 @@ import os
 import re
 import sys
 import tempfile
+import time
 
 import numpy as np
 
@@ -69,6 +72,7 @@ def main():
     ap.add_argument("--name", default="bvh_builder")
     ap.add_argument("--soup", type=int, default=1_000_000)
     ap.add_argument("--skip-soup", action="store_true")
+    ap.add_argument("--derive", default="host", help="comma-separated derivations to measure: host, device")
     a = ap.parse_args()
     rows = []
     ctx = Context(0)
@@ -78,11 +82,17 @@ def main():
             jobs.append((f"soup_{a.soup}", parse_job(soup_scene(tmp, a.soup))))
         for name, job in jobs:
             for builder in ("host", "device"):
-                for k in range(4):                               # upload 0 warms up
-                    ctx.upload(job, bvh=builder)
-                    bi = ctx.bvh_build_info()
-                    rows.append({"kind": "build", "scene": name, "builder": builder, "upload": k, "warmup": k == 0, **bi})
-                    print(json.dumps(rows[-1]), flush=True)
+                for derive in a.derive.split(","):
+                    for k in range(4):                           # upload 0 warms up
+                        t0 = time.perf_counter()
+                        ctx.upload(job, bvh=builder, derive=derive)
+                        ms_upload = (time.perf_counter() - t0) * 1e3
+                        bi, di = ctx.bvh_build_info(), ctx.derive_info()
+                        rows.append({"kind": "build", "scene": name, "builder": builder, "derive": derive, "upload": k,
+                                     "warmup": k == 0, **bi, "derive_used": di["used"], "bvh4_nodes": di["bvh4_nodes"],
+                                     "level_launches": di["level_launches"], "ms_derive_device": di["ms_derive_device"],
+                                     "ms_plan_host": di["ms_plan_host"], "ms_upload": ms_upload})
+                        print(json.dumps(rows[-1]), flush=True)
                 if name == "ducky":
                     _, st = ctx.render_pass(seed=0x0B11A6, pass_index=0, flags=_ffi.PASS_TRAVERSAL_STATS | _ffi.PASS_KERNEL_TIMING)
                     rows.append({"kind": "walk", "scene": name, "builder": builder, "node_visits": int(st.node_visits),
